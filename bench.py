@@ -17,6 +17,19 @@ their residual plane is zero, so the x2f16 GEMMs run 2 products instead of 3
 ``processed_weights_leg`` re-times the sweep on the TL-processed weights
 (3 products) for comparison.
 
+A plain run (``--gpus 1 --steps K --warmup W``) does what the headline needs and
+no more: it builds the model, extracts the means, warms up, times the K steps
+and prints the result line (``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step`` = milliseconds per timed step,
+``config``, ``algorithmic``).  ``--dump-outputs DIR`` also writes the last timed
+step's result (``cie_sums.npy``: the [L, H] float32 CIE sums) for an
+output-by-output comparison of two builds; every input is seeded.  Everything
+else below — the profiled pass behind ``roofline`` / ``hbm_kernels`` and the
+extraction timing, ``processed_weights_leg``, ``f32_leg``,
+``weak_prompt_partition``, ``cpu_baseline`` with ``parity`` /
+``parity_bench_weights`` and ``configs`` — runs after the headline under
+``--full`` only.
+
 GEMMs (95 % of the step) run on the fp32-accurate two-plane fp16 split
 (``--gemm x2f16``, default: every fp32 operand split into 2 power-of-two-scaled
 fp16 planes, 3 products on v_mfma_f32_16x16x32_f16, fp32 accumulation — the
@@ -152,7 +165,19 @@ def parse():
                          "the workload string says so, and 0 (default) is the BASELINE config")
     ap.add_argument("--launch-check", dest="launch_check", action="store_true",
                     help="only the rank launch, rendezvous and max-over-ranks timing (no GPU work; CPU test)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the bench measures or checks: the profiled "
+                         "pass (roofline, hbm_kernels, extraction timing), the processed-weights / f32 / weak legs, "
+                         "the CPU baseline with both parity blocks and the other configs (each still has its own "
+                         "--no-... switch); without it a run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what the last timed step returned to DIR/<name>.npy "
+                         "(cie_sums: the all-reduced [L, H] float32 CIE sums); the inputs are seeded, so two builds "
+                         "run with the same arguments can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port() -> int:
@@ -271,6 +296,18 @@ def hbm_kernels(hbm, hbm_ex, steps, workload=None):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(directory, arrays):
+    """``--dump-outputs DIR``: what the last timed step returned to its caller,
+    one ``DIR/<name>.npy`` per array (float32, or float64 where the step
+    computed in it)."""
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        np.save(d / f"{name}.npy", a.numpy() if a.dtype == torch.float64 else a.float().numpy())
 
 
 SPLITS = {"sites": "sites in balanced layer-pair blocks per rank", "heads": "sites h = rank (mod {n})"}
@@ -713,16 +750,18 @@ def main():
         random.seed(4321)
         pairs = tvr_amd.tasks.synthetic_task(52, cfg.d_vocab, seed=7)
         ex_prompts = tvr_amd.prompts.sample_icl_prompts(model, pairs, "→", ",", args.extract, 6)
-        sum_last_z(model, ex_prompts[:64])  # workspace sizing outside the timed extraction
-        torch.cuda.synchronize()
-        te = time.perf_counter()
+        if args.full:
+            sum_last_z(model, ex_prompts[:64])  # workspace sizing outside the timed extraction
+            torch.cuda.synchronize()
+            te = time.perf_counter()
         zsum = sum_last_z(model, ex_prompts)
-        torch.cuda.synchronize()
-        te = time.perf_counter() - te
-        model.profile(True)  # kernel timings of the capture from a separate profiled pass
-        sum_last_z(model, ex_prompts)
-        hbm_ex = model.profile_hbm_stats()
-        model.profile(False)
+        if args.full:
+            torch.cuda.synchronize()
+            te = time.perf_counter() - te
+            model.profile(True)  # kernel timings of the capture from a separate profiled pass
+            sum_last_z(model, ex_prompts)
+            hbm_ex = model.profile_hbm_stats()
+            model.profile(False)
         n_ex = len(ex_prompts)
         mean = model.project_heads(zsum) / n_ex
     else:
@@ -794,37 +833,20 @@ def main():
     elapsed, cie = timed(args.warmup, args.steps, False)
     rank_elapsed = list(rank_times)
     value = units_total * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"cie_sums": cie})
 
-    # --- roofline of the dominant kernel + HBM-bound kernels: a separate profiled pass
-    psteps = max(1, args.profile_steps)
-    el_prof, _ = timed(0, psteps, True)
-    st = model.profile_stats()
-    hbm = model.profile_hbm_stats()
-    model.profile(False)
-    fam = st["all"]
-    achieved = fam["flops"] / (fam["ms"] * 1e-3) / 1e12
     T = len(prompts[0])
     workload, scaling = describe_workload(args.model, cfg.n_layers, cfg.n_heads, args.prompts, args.kshot, T, world,
                                           shard, emulate, len(sites))
     if model.exact16 and args.gemm == "x2f16":  # another kernel instruction mix: 3-product counters do not apply
         workload += ", fp16-valued weights (exact-fp16 GEMMs, 2 products)"
-    pmc, traffic_src = pmc_summary(args.gemm, workload)
-    traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
     products = 2 if (args.gemm == "x2f16" and model.exact16) else PRODUCTS.get(args.gemm)
     peak = BF16_MFMA_PEAK_TFLOPS / products if products else PEAKS[args.gemm]
     L, d, V = cfg.n_layers, cfg.d_model, cfg.d_vocab
     P_l = 4 * d * d + 2 * d * cfg.d_mlp
     # F_alg(site at layer l) = (L-1-l)(2 P_l T + 2 T(T+1) d) + 2 d V
     f_alg = sum((L - 1 - l) * (2 * P_l * T + 2 * T * (T + 1) * d) + 2 * d * V for l in range(L)) / L
-    variants = {}
-    for name in ("qkv_mlpin", "o_mlpout", "unembed"):
-        v = st[name]
-        if v["launches"]:
-            variants[name] = {"launches": v["launches"],
-                              "achieved_tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
-                              "avg_launch_ms": round(v["ms"] / v["launches"], 4),
-                              "alg_bytes_per_launch": round(v["bytes"] / v["launches"]),
-                              "share_of_gemm_time": round(v["ms"] / fam["ms"], 4)}
     parallelism = ("single GPU" if world == 1 else
                    f"{SPLITS[shard].format(n=world)} (same {args.prompts} prompts on every GPU), weights replicated, "
                    f"1 all-reduce of [L,H] per step" if shard in SPLITS else
@@ -853,7 +875,40 @@ def main():
             "dist_backend": args.dist_backend if world > 1 else None,
             "rank_elapsed_s": [round(x, 4) for x in rank_elapsed] if world > 1 else None,
         },
-        "roofline": {
+        "algorithmic": {
+            "gflop_per_site": round(f_alg / 1e9, 2),
+            "site_tflops": round(value * f_alg / 1e12, 2),
+            # BASELINE.md section 3's roofline fraction: the reference's algorithmic work per site
+            # (SURVEY section 8d) x sites/s over the whole timed step, against the same peak
+            # (work the engine skips -- shared prefixes, the trimmed last layer, the linearised
+            # entry layer -- counts as done, as in the reference's loop)
+            "site_frac": round(value * f_alg / 1e12 / peak, 4),
+        },
+    }
+    out["config"]["gemm"] = args.gemm
+    out["config"]["weights"] = args.weights
+    out["config"]["exact16_gemms"] = bool(model.exact16 and args.gemm == "x2f16")  # (bf16 mode leaves them unused)
+    if args.full:
+        # --- roofline of the dominant kernel + HBM-bound kernels: a separate profiled pass
+        psteps = max(1, args.profile_steps)
+        el_prof, _ = timed(0, psteps, True)
+        st = model.profile_stats()
+        hbm = model.profile_hbm_stats()
+        model.profile(False)
+        fam = st["all"]
+        achieved = fam["flops"] / (fam["ms"] * 1e-3) / 1e12
+        pmc, traffic_src = pmc_summary(args.gemm, workload)
+        traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
+        variants = {}
+        for name in ("qkv_mlpin", "o_mlpout", "unembed"):
+            v = st[name]
+            if v["launches"]:
+                variants[name] = {"launches": v["launches"],
+                                  "achieved_tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
+                                  "avg_launch_ms": round(v["ms"] / v["launches"], 4),
+                                  "alg_bytes_per_launch": round(v["bytes"] / v["launches"]),
+                                  "share_of_gemm_time": round(v["ms"] / fam["ms"], 4)}
+        out["roofline"] = {
             "bound": "mfma",
             "kernel": KERNELS["x2f16-exact16" if (args.gemm == "x2f16" and model.exact16) else args.gemm],
             "achieved": round(achieved, 2),
@@ -875,23 +930,10 @@ def main():
             "avg_launch_ms": round(fam["ms"] / max(fam["launches"], 1), 4),
             "gemm_share_of_step": round(fam["ms"] / (el_prof * 1e3), 4),
             "variants": variants,
-        },
-        "hbm_kernels": hbm_kernels(hbm, hbm_ex, psteps, workload),
-        "algorithmic": {
-            "gflop_per_site": round(f_alg / 1e9, 2),
-            "site_tflops": round(value * f_alg / 1e12, 2),
-            # BASELINE.md section 3's roofline fraction: the reference's algorithmic work per site
-            # (SURVEY section 8d) x sites/s over the whole timed step, against the same peak
-            # (work the engine skips -- shared prefixes, the trimmed last layer, the linearised
-            # entry layer -- counts as done, as in the reference's loop)
-            "site_frac": round(value * f_alg / 1e12 / peak, 4),
-            "extraction_prompts_per_s": round(n_ex / te, 1) if te else None,
-        },
-    }
-    out["config"]["gemm"] = args.gemm
-    out["config"]["weights"] = args.weights
-    out["config"]["exact16_gemms"] = bool(model.exact16 and args.gemm == "x2f16")  # (bf16 mode leaves them unused)
-    if world == 1 and model.exact16 and args.gemm == "x2f16" and not emulate and args.processed_leg:
+        }
+        out["hbm_kernels"] = hbm_kernels(hbm, hbm_ex, psteps, workload)
+        out["algorithmic"]["extraction_prompts_per_s"] = round(n_ex / te, 1) if te else None
+    if args.full and world == 1 and model.exact16 and args.gemm == "x2f16" and not emulate and args.processed_leg:
         # the same sweep on the TL-processed weights (3 products: the path of fp32-valued checkpoints)
         model.set_exact16(False)
         npw = max(1, min(args.steps, 2))
@@ -902,7 +944,7 @@ def main():
             "value": round(units_rank * npw / el_pw, 2),
             "max_abs_cie_diff_vs_exact16": float((cie - cie_pw).abs().max()),
             "max_abs_cie": float(cie_pw.abs().max())}
-    if world == 1 and args.f32_leg and args.gemm != "f32":
+    if args.full and world == 1 and args.f32_leg and args.gemm != "f32":
         model.set_gemm("f32")
         n32 = max(1, min(args.steps, 2))
         el32, cie32 = timed(1, n32, False)
@@ -915,7 +957,7 @@ def main():
         }
     if emulate:
         out["emulated_world"] = emulate
-    if world > 1 and shard in SPLITS and args.weak_leg:
+    if args.full and world > 1 and shard in SPLITS and args.weak_leg:
         # the weak form (own prompts per rank, every site): reported beside the strong headline, never as `value`
         prompts, answers = tvr_amd.prompts.synthetic_cie_prompts(model, args.prompts, args.kshot, seed=1234 + rank)
         sites = everything
@@ -926,7 +968,7 @@ def main():
                                           "prompts")[0],
             "steps": nw, "value": round(len(prompts) * cfg.n_layers * cfg.n_heads * world * nw / el_w, 2),
             "unit": "patched prompts/s", "scaling": "weak", "rank_elapsed_s": [round(x, 4) for x in rank_times]}
-    if rank == 0 and world == 1 and args.cpu_baseline and not emulate:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline and not emulate:
         out["cpu_baseline"], out["parity_bench_weights"] = cpu_baseline(args, cfg, prompts, answers, mean, model)
         try:
             out["parity"] = parity_informative(args, dev, out["cpu_baseline"]["cores"])
@@ -935,7 +977,7 @@ def main():
     # the other BASELINE.json configs, timed after the headline (never part of `value`): C2 is a one-GPU config
     # (N = 1 only); C4 and C5 are BASELINE's 8-GPU configs, sharded over the ranks at N > 1;
     # --emulate-world times C5's rank-0 share
-    which = {c for c in args.configs.split(",") if c} if args.model == "pythia-2.8b" else set()
+    which = {c for c in args.configs.split(",") if c} if args.full and args.model == "pythia-2.8b" else set()
     if world > 1:
         which -= {"C2"}
     if emulate:

@@ -68,6 +68,44 @@ def test_hbm_kernels_pmc_traffic_keyed_on_workload():
     assert all("traffic" not in (other[k] or {}) for k in ("entry", "lnpre", "attention", "row_stats"))
 
 
+def _parse(*argv):
+    import sys
+    saved = sys.argv
+    try:
+        sys.argv = ["bench.py", *argv]
+        return bench.parse()
+    finally:
+        sys.argv = saved
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """A plain run times the headline only; the legs keep their own switches
+    (on by default) and run under ``--full``."""
+    a = _parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = _parse("--full", "--no-f32-leg", "--dump-outputs", "somewhere")
+    assert a.full is True and a.dump_outputs == "somewhere"
+    assert a.f32_leg is False and a.cpu_baseline and a.processed_leg and a.weak_leg and a.configs == "C2,C4,C5"
+
+
+def test_steps_must_be_positive():
+    import pytest
+    with pytest.raises(SystemExit):
+        _parse("--steps", "0")
+
+
+def test_dump_outputs_writes_float_npy(tmp_path):
+    import numpy as np
+    import torch
+    cie = torch.arange(12, dtype=torch.float32).reshape(3, 4) * 1e-6
+    d64 = cie.double() / 3
+    bench.dump_outputs(tmp_path / "new" / "dir", {"cie_sums": cie, "d": d64, "h": cie.half()})
+    out = np.load(tmp_path / "new" / "dir" / "cie_sums.npy")
+    assert out.dtype == np.float32 and out.shape == (3, 4) and np.array_equal(out, cie.numpy())
+    assert np.load(tmp_path / "new" / "dir" / "d.npy").dtype == np.float64
+    assert np.load(tmp_path / "new" / "dir" / "h.npy").dtype == np.float32
+
+
 def test_gpus_flag_launches_ranks_itself():
     """``bench.py --gpus 2`` without torchrun starts 2 ranks of itself (the
     parent never touches a GPU) and rank 0 reports the world size the process

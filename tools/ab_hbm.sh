@@ -12,7 +12,7 @@ for r in $(seq 1 $ROUNDS); do
   for var in ${LIBS//,/ }; do
     lib=${var##*:}; ev=""; [ "$lib" != "$var" ] && ev=${var%:*}
     n=$(basename $(dirname $lib))_$(basename $lib .so)${ev:+_${ev//[=+]/_}}_$r
-    env ${ev//+/ } TVR_LIB=$lib timeout -k 10 300 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-f32-leg \
+    env ${ev//+/ } TVR_LIB=$lib timeout -k 10 300 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-f32-leg \
         --no-processed-leg --extract 0 --configs= "$@" > $OUT/$n.json 2> $OUT/$n.err || { tail -5 $OUT/$n.err; exit 1; }
     python3 -c "
 import json, sys

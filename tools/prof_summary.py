@@ -171,7 +171,7 @@ def main():
     ap.add_argument("--write")
     ap.add_argument("--mfma", help="PMC pass with SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE and the SQ wave states")
     ap.add_argument("--bench", help="bench.py JSON of the same command (algorithmic bytes per launch)")
-    ap.add_argument("--cmd", default="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-f32-leg")
+    ap.add_argument("--cmd", default="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-f32-leg")
     ap.add_argument("--out", default=str(ROOT / "profiles"), help="summary directory")
     a = ap.parse_args()
     out_dir = Path(a.out)

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/scaling_$TAG
 RAW=/tmp/scal_raw
 mkdir -p $OUT $RAW
 cd /tmp
-B="$R/bench.py --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-f32-leg --extract 0 --configs="
+B="$R/bench.py --full --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-f32-leg --extract 0 --configs="
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/n1 -o run -- python3 $B > $OUT/n1.json 2> $OUT/n1.err && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/em -o run -- python3 $B --emulate-world $N --shard $SH > $OUT/em.json 2> $OUT/em.err && \
 python3 $R/tools/scaling_compare.py $RAW/n1 $RAW/em $N > $OUT/compare.txt
