@@ -65,7 +65,16 @@ enum tvr_site_kind {
   /* blocks.{layer}.hook_resid_pre of sequence `seq` with row `pos` replaced by
    * the same hook's row `src_pos` of sequence `src_seq`, then
    * forward(start_at_layer=layer) (scratch.py:140-143, 201-209). */
-  TVR_SITE_SET_RESID_PRE_POS = 3
+  TVR_SITE_SET_RESID_PRE_POS = 3,
+  /* Joint head-set patches (tvr_patch_sweep_sets only): for EVERY member
+   * (layer, head, vec) of the site's set,
+   *   blocks.{layer}.attn.hook_result[0,:,head,:] = vectors[vec]   (ALLPOS:
+   *   one scratch2.py:188 hook per member in one run_with_hooks call), or
+   *   blocks.{layer}.attn.hook_result[0,-1,head,:] = vectors[vec]  (LASTPOS:
+   *   the last-token intervention of the function-vector paper).
+   * The site's own layer / head / vec fields are ignored. */
+  TVR_SITE_REPLACE_HEADSET_ALLPOS = 4,
+  TVR_SITE_REPLACE_HEADSET_LASTPOS = 5
 };
 
 typedef struct tvr_config {
@@ -260,6 +269,49 @@ int tvr_patch_sweep(tvr_model* model, tvr_trace* trace,
                     const float* vectors, int32_t n_vectors, float* out_prob,
                     int32_t* out_topk, int32_t topk, float* out_logits,
                     void* stream);
+/* (tvr_patch_sweep takes kinds 0-3; it rejects the head-set kinds 4 and 5 with
+ * TVR_ERR_INVALID and a message naming tvr_patch_sweep_sets.) */
+
+/* tvr_patch_sweep with head-set sites: one patched forward replaces the
+ * hook_result of a SET of (layer, head) pairs at once — the joint mean-ablation
+ * / joint patching of the function-vector paper, which the reference side
+ * writes as one run_with_hooks call with one scratch2.py:188 hook per member.
+ *   set_off  host [n_sites + 1], non-decreasing, set_off[0] >= 0: a site of
+ *            kind TVR_SITE_REPLACE_HEADSET_ALLPOS / _LASTPOS owns
+ *            patches[set_off[i] .. set_off[i+1]); a site of kinds 0-3 must own
+ *            an empty range and behaves exactly as in tvr_patch_sweep (mixed
+ *            launches are fine).  An empty set equals TVR_SITE_NONE.
+ *   patches  host [set_off[n_sites]] (the caller guarantees that length; may be
+ *            NULL when every set is empty).  layer in [0, n_layers), head in
+ *            [0, n_heads), vec in [0, n_vectors); the same (layer, head) twice
+ *            in one set is an error.  The vectors of one (site, layer) are
+ *            summed in list order (fp32), so results are reproducible bit for
+ *            bit for a given list.
+ *   vectors  device [n_vectors][d], any vectors (not only ones in the row
+ *            space of W_O[head]): head h of layer l is replaced by zeroing its
+ *            d_head columns of that layer's O-projection input and adding the
+ *            vector to the residual rows the projection accumulates into.
+ *            Alignment: for the head-set kinds float (4 B) suffices — a base
+ *            that is not 16-byte aligned takes an element-wise variant of the
+ *            head-set kernel instead of the float4 one.  The kernels of
+ *            TVR_SITE_REPLACE_HEAD_ALLPOS read `vectors` with 16-byte loads:
+ *            a launch that holds such a site with a base that is not 16-byte
+ *            aligned returns TVR_ERR_INVALID here (tvr_patch_sweep does not
+ *            check: pass it a 16-byte aligned base).
+ * A set site enters the staircase at its lowest patched layer and computes
+ * every layer from there (ALLPOS: all T rows; LASTPOS: the last row, against
+ * the clean K/V).  Works on a filled trace and on a deferred clean forward, on
+ * every GEMM path.  All arguments are validated before any device call:
+ * TVR_ERR_INVALID for null arguments, decreasing offsets, a layer / head / vec
+ * out of range, a duplicate (layer, head), patches owned by a site of kinds 0-3.
+ * Outputs as tvr_patch_sweep.  (Backward-compatible addition: ABI 11.) */
+typedef struct tvr_head_patch { int32_t layer, head, vec; } tvr_head_patch;
+int tvr_patch_sweep_sets(tvr_model* model, tvr_trace* trace,
+                         const tvr_site* sites, int32_t n_sites,
+                         const int32_t* set_off, const tvr_head_patch* patches,
+                         const float* vectors, int32_t n_vectors, float* out_prob,
+                         int32_t* out_topk, int32_t topk, float* out_logits,
+                         void* stream);
 
 /* out[l][h][:] = zsum[l][h*d_head:(h+1)*d_head] @ W_O[l,h]: turns the z-form
  * capture into the hook_result form of scratch2.py:98 (sum over prompts). */
@@ -328,7 +380,9 @@ int tvr_profile_read(tvr_model* model, tvr_kernel_stats* out);
  * bytes / ms.  Index = enum tvr_hbm_kind. */
 enum tvr_hbm_kind {
   TVR_HBM_ENTRY = 0,      /* patch injection at the entry layer (REPLACE_HEAD / ADD / SET_RESID):
-                           * clean rows in, patched rows out, z rows + W_O slice per head */
+                           * clean rows in, patched rows out, z rows + W_O slice per head; and the head-set
+                           * patches of tvr_patch_sweep_sets, one launch per patched layer: z slices zeroed +
+                           * residual rows read and written + vectors read */
   TVR_HBM_CAPTURE = 1,    /* extraction: sum of hook_z at every prompt's last row -> [d] per layer */
   TVR_HBM_LNPRE = 2,      /* LayerNormPre rows -> GEMM input format */
   TVR_HBM_ATTENTION = 3,  /* attention: fp32 Q/K/V rows in, z out (activation format [+ fp32 hook_z]) */

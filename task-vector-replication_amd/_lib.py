@@ -36,6 +36,8 @@ SITE_NONE = 0
 SITE_REPLACE_HEAD_ALLPOS = 1
 SITE_ADD_ATTN_OUT_LASTPOS = 2
 SITE_SET_RESID_PRE_POS = 3
+SITE_REPLACE_HEADSET_ALLPOS = 4  # tvr_patch_sweep_sets only
+SITE_REPLACE_HEADSET_LASTPOS = 5
 
 c_f32p = ctypes.c_void_p
 c_i32p = ctypes.c_void_p
@@ -57,6 +59,10 @@ class CSite(ctypes.Structure):
 
 
 SITE_FIELDS = [f for f, _ in CSite._fields_]
+
+
+class CHeadPatch(ctypes.Structure):
+    _fields_ = [("layer", ctypes.c_int32), ("head", ctypes.c_int32), ("vec", ctypes.c_int32)]
 
 
 class CKernelStats(ctypes.Structure):
@@ -105,6 +111,9 @@ SIGNATURES = {
     "tvr_patch_sweep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                        c_f32p, ctypes.c_int32, c_f32p, c_i32p, ctypes.c_int32, c_f32p,
                                        ctypes.c_void_p]),
+    "tvr_patch_sweep_sets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                            c_i32p, ctypes.c_void_p, c_f32p, ctypes.c_int32, c_f32p, c_i32p,
+                                            ctypes.c_int32, c_f32p, ctypes.c_void_p]),
     "tvr_project_heads": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p]),
     "tvr_gemm_f32": (ctypes.c_int, [c_f32p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p, c_f32p,
                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -143,6 +152,8 @@ SIGNATURES = {
 OPS_PATH = LIB_PATH.parent / OPS_NAME
 # the torch.library operators _tvr_ops.so registers (csrc/torch_ops.cpp)
 OPS = ("forward_clean", "patch_sweep", "project_heads", "forward_logits")
+# the joint head-set sweep (tvr_patch_sweep_sets), registered by the same extension
+SET_OPS = ("patch_sweep_sets",)
 
 _LIB = None
 _OPS_LOADED = False

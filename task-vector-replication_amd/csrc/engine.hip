@@ -33,6 +33,7 @@
 #include "kernels.hpp"
 #include "lin_entry.hpp"
 #include "entry_mfma.hpp"
+#include "headset_patch.hpp"
 
 using namespace tvr;
 
@@ -991,6 +992,13 @@ struct Acts {
   float* resid_mirror = nullptr;
   float* qkv_mirror = nullptr;
   int mirror_rows = 0;
+  // head-set sites with patches at the layer being run (tvr_patch_sweep_sets): applied to a2's z columns
+  // and resid between the attention and the O + MLP-out GEMM (apply_headset); hs_n == 0: none
+  const HeadsetItem* hs_items = nullptr;
+  const HeadsetPatch* hs_patches = nullptr;
+  const float* hs_vectors = nullptr;
+  int hs_n = 0, hs_max_rows = 0;
+  double hs_bytes = 0.0;  // algorithmic bytes of the launch (profiling)
 };
 
 // z: the z columns of a2 (fp32 or activation format fmt); zf: optional fp32 copy [rows][d].
@@ -1175,6 +1183,31 @@ int launch_w1(tvr_model* m, int l, const void* xn, int M, int c0, int N, const G
   return launch_gemm(epi, xn, d, fmt, m->w1[l].rows((size_t)(c0 + nqk) * d), d, M, N - nqk, d, e, st, m);
 }
 
+// The layer's head-set patches (headset_patch.hpp), after the attention has written z and before the
+// O + MLP-out GEMM reads it: zero the listed heads' z slices, add their vectors to the residual rows.
+int apply_headset(tvr_model* m, const Acts& a, hipStream_t st) {
+  if (a.hs_n <= 0) return TVR_OK;
+  const tvr_config& c = m->cfg;
+  const int d = c.d_model;
+  const bool planar = a.fmt != ACT_F32;
+  const size_t row_bytes = (size_t)m->K2 * 4;  // fp32 [K2], or halves [2][K2]
+  const int slice_bytes = c.d_head * (planar ? 2 : 4);
+  const int n_planes = a.fmt == ACT_X2F16 ? 2 : 1;
+  const size_t plane_bytes = (size_t)m->K2 * 2;
+  const dim3 g(a.hs_n, (a.hs_max_rows + HEADSET_ROWS - 1) / HEADSET_ROWS);
+  const bool v4 = ((uintptr_t)a.hs_vectors & 15) == 0 && d % 4 == 0;
+  ProfSpan ps(m, st);
+  if (v4)
+    hipLaunchKernelGGL(headset_patch_kernel<true>, g, dim3(HEADSET_THREADS), 0, st, a.hs_items, a.hs_patches,
+                       a.hs_vectors, (char*)a.a2, row_bytes, slice_bytes, n_planes, plane_bytes, a.resid, d);
+  else
+    hipLaunchKernelGGL(headset_patch_kernel<false>, g, dim3(HEADSET_THREADS), 0, st, a.hs_items, a.hs_patches,
+                       a.hs_vectors, (char*)a.a2, row_bytes, slice_bytes, n_planes, plane_bytes, a.resid, d);
+  TVR_HIP(hipGetLastError());
+  ps.done(TVR_HBM_ENTRY, a.hs_bytes);
+  return TVR_OK;
+}
+
 // zf_last: the fp32 hook_z copy of each sequence's last row only, at row s of zf
 int run_block(tvr_model* m, int l, int R, const SeqDesc* d_seqs, int n_seqs, int maxT,
               Acts& a, float* qkv_out, const float* cache_qkv, float* zf, hipStream_t st, bool zf_last = false,
@@ -1225,6 +1258,7 @@ int run_block_last_rows(tvr_model* m, int l, int R, const SeqDesc* d_seqs, int n
                            row_from));
   ps.done(TVR_HBM_ATTENTION, attention_bytes(d, n_last, R, a.fmt, zf ? std::min(n_last, zf_rows) : 0));
   if (!write_out) return TVR_OK;
+  TVR_TRY(apply_headset(m, a, st));  // global row indices, as d_last's (rows the GEMM does not gather are unread)
   GemmEpi e2{};
   e2.bias = w.b2;
   e2.out0 = a.resid;
@@ -1240,6 +1274,7 @@ int run_block_last_rows(tvr_model* m, int l, int R, const SeqDesc* d_seqs, int n
 int run_block_out(tvr_model* m, int l, int R, Acts& a, hipStream_t st) {
   const int d = m->cfg.d_model;
   const tvr_layer_weights& w = m->layers[l];
+  TVR_TRY(apply_headset(m, a, st));
   GemmEpi e2{};
   e2.bias = w.b2;
   e2.out0 = a.resid;
@@ -2030,11 +2065,15 @@ int tvr_forward_logits(tvr_model* m, const int32_t* tokens, const float* resid_i
 
 
 
-int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32_t n_sites,
-                    const float* vectors, int32_t n_vectors, float* out_prob, int32_t* out_topk,
-                    int32_t topk, float* out_logits, void* stream) {
+// The body of tvr_patch_sweep and tvr_patch_sweep_sets.  set_off == nullptr: the plain sweep (kinds 0-3
+// only); else sites of kinds 4 / 5 own patches[set_off[i], set_off[i + 1]) and the other kinds own nothing.
+// Without set sites every head-set table is empty and no launch is added.
+static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32_t n_sites,
+                      const int32_t* set_off, const tvr_head_patch* patches, const float* vectors,
+                      int32_t n_vectors, float* out_prob, int32_t* out_topk, int32_t topk, float* out_logits,
+                      void* stream) {
   if (!m || !trace || !sites || n_sites <= 0)
-    return fail(TVR_ERR_INVALID, "tvr_patch_sweep: bad argument");
+    return fail(TVR_ERR_INVALID, std::string(fn) + ": bad argument");
   if (trace->model != m) return fail(TVR_ERR_INVALID, "trace belongs to another model");
   if (trace->n_seq <= 0) return fail(TVR_ERR_INVALID, "trace is empty: run tvr_forward_clean first");
   if (topk < 0 || topk > STATS_MAX_K) return fail(TVR_ERR_INVALID, "topk must be in [0, 16]");
@@ -2061,6 +2100,37 @@ int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32
       return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": seq out of range");
     const int T = trace->seq_len[s.seq];
     maxT = std::max(maxT, T);
+    const bool is_set = s.kind == TVR_SITE_REPLACE_HEADSET_ALLPOS || s.kind == TVR_SITE_REPLACE_HEADSET_LASTPOS;
+    if (is_set && !set_off)
+      return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": head-set kinds (4, 5) go through tvr_patch_sweep_sets");
+    if (set_off && !is_set && set_off[i + 1] != set_off[i])
+      return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": only head-set kinds (4, 5) own patches");
+    if (is_set) {
+      // Head-set site: enters at its lowest patched layer as an unpatched copy of the clean rows (the
+      // entry kernel's row copy) and runs every layer from there, patched by headset_patch_kernel at
+      // each layer where it has heads.  An empty set is TVR_SITE_NONE.
+      int l_min = L;
+      std::vector<std::pair<int, int>> lh;
+      for (int q = set_off[i]; q < set_off[i + 1]; ++q) {
+        const tvr_head_patch& hp = patches[q];
+        if (hp.layer < 0 || hp.layer >= L || hp.head < 0 || hp.head >= c.n_heads)
+          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": patch layer/head out of range");
+        if (!vectors || hp.vec < 0 || hp.vec >= n_vectors)
+          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": patch vector out of range");
+        l_min = std::min(l_min, (int)hp.layer);
+        lh.emplace_back(hp.layer, hp.head);
+      }
+      std::sort(lh.begin(), lh.end());
+      if (std::adjacent_find(lh.begin(), lh.end()) != lh.end())
+        return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": the same (layer, head) twice in one set");
+      entry[i] = l_min;
+      if (s.kind == TVR_SITE_REPLACE_HEADSET_ALLPOS && l_min < L) {
+        p0[i] = 0; nrow[i] = T;
+      } else {
+        p0[i] = T - 1; nrow[i] = 1;
+      }
+      continue;
+    }
     switch (s.kind) {
       case TVR_SITE_NONE:
         entry[i] = L; p0[i] = T - 1; nrow[i] = 1;
@@ -2070,6 +2140,8 @@ int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32
           return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": layer/head out of range");
         if (!vectors || s.vec < 0 || s.vec >= n_vectors)
           return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": vector out of range");
+        if (set_off && ((uintptr_t)vectors & 15))  // tvr.h: the head-replacement entry kernels load 16 bytes
+          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": REPLACE_HEAD_ALLPOS needs 16-byte aligned vectors");
         entry[i] = s.layer + 1; p0[i] = 0; nrow[i] = T;
         break;
       case TVR_SITE_ADD_ATTN_OUT_LASTPOS:
@@ -2159,7 +2231,8 @@ int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32
     seqs[nc + k] = leader[i] >= 0 ? SeqDesc{Rc + row0[i], nrow[i], p0[i], Rc + row0[leader[i]], 0, 1}
                                   : SeqDesc{Rc + row0[i], nrow[i], p0[i], srow, 0, 0};
     EntryDesc e{};
-    e.kind = s.kind;
+    // a head-set site enters as a plain copy of its clean rows (the entry kernel's TVR_SITE_NONE path)
+    e.kind = s.kind >= TVR_SITE_REPLACE_HEADSET_ALLPOS ? (int32_t)TVR_SITE_NONE : s.kind;
     e.row0 = Rc + row0[i];
     e.n = nrow[i];
     e.p0 = p0[i];
@@ -2229,6 +2302,34 @@ int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32
   for (int s = 0; s < nc; ++s) clean_last[s] = trace->seq_off[s] + trace->seq_len[s] - 1;
   if (fused && !trace->p_targets.empty()) clean_tg = trace->p_targets;
   const int ktop = std::max(topk, fused ? trace->p_k : 0);
+
+  // Head-set tables (headset_patch.hpp): per layer, one item per site with heads there (entry order) and
+  // the items' (head, vector) lists, each in the caller's order.
+  std::vector<HeadsetItem> hs_items;
+  std::vector<HeadsetPatch> hs_patches;
+  std::vector<int> hs_beg(L + 1, 0), hs_max_rows(L, 0);
+  std::vector<double> hs_bytes(L, 0.0);
+  if (set_off && set_off[n_sites] > set_off[0]) {
+    const double slice = (double)c.d_head * (act_fmt(m) == ACT_F32 ? 4.0 : act_fmt(m) == ACT_X2F16 ? 4.0 : 2.0);
+    std::vector<std::vector<std::pair<int, int>>> by_layer(L);  // (site, patch) in (entry order, list order)
+    for (int k = 0; k < n_sites; ++k)
+      for (int q = set_off[order[k]]; q < set_off[order[k] + 1]; ++q) by_layer[patches[q].layer].emplace_back(order[k], q);
+    for (int l = 0; l < L; ++l) {
+      hs_beg[l] = (int)hs_items.size();
+      const auto& bl = by_layer[l];
+      for (size_t x = 0; x < bl.size();) {
+        const int i = bl[x].first, first = (int)hs_patches.size();
+        for (; x < bl.size() && bl[x].first == i; ++x)
+          hs_patches.push_back(HeadsetPatch{patches[bl[x].second].head, patches[bl[x].second].vec});
+        const int np = (int)hs_patches.size() - first;
+        hs_items.push_back(HeadsetItem{Rc + row0[i], nrow[i], first, np});
+        hs_max_rows[l] = std::max(hs_max_rows[l], nrow[i]);
+        // slices zeroed + residual rows read and written + vectors read
+        hs_bytes[l] += (double)nrow[i] * (8.0 * d + slice * np) + 4.0 * d * np;
+      }
+    }
+    hs_beg[L] = (int)hs_items.size();
+  }
 
   // Linearised entry layers (lin_entry.hpp): layer l in [1, L-2] of a fused
   // sweep whose entering sites are all REPLACE_HEAD computes its entering
@@ -2308,6 +2409,8 @@ int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32
   const size_t o_lin_vids = cv.take<int32_t>(lin_vids.size());
   const size_t o_egidx = cv.take<int32_t>(egidx.size());
   const size_t o_egroups = cv.take<int2>(egroups.size());
+  const size_t o_hs_items = cv.take<HeadsetItem>(hs_items.size());  // (empty without set sites: no bytes)
+  const size_t o_hs_patches = cv.take<HeadsetPatch>(hs_patches.size());
   const size_t o_resid = cv.take<float>((size_t)RA * d);
   const size_t o_xn = cv.take<float>((size_t)RA * d);
   const size_t o_xn2 = use_x16(m) ? cv.take<float>((size_t)RA * d) : 0;
@@ -2344,6 +2447,10 @@ int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32
   }
   ub.add(o_egidx, egidx);
   ub.add(o_egroups, egroups);
+  if (!hs_items.empty()) {
+    ub.add(o_hs_items, hs_items);
+    ub.add(o_hs_patches, hs_patches);
+  }
   TVR_TRY(flush_uploads(m, st, base, ub));
 
   const int fmt = act_fmt(m);
@@ -2527,6 +2634,14 @@ int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32
     }
     TVR_TRY(enter(l));
     if (Rl == 0) continue;
+    a.hs_n = hs_beg[l + 1] - hs_beg[l];  // this layer's head-set patches (0 without set sites)
+    if (a.hs_n > 0) {
+      a.hs_items = (const HeadsetItem*)(base + o_hs_items) + hs_beg[l];
+      a.hs_patches = (const HeadsetPatch*)(base + o_hs_patches);
+      a.hs_vectors = vectors;
+      a.hs_max_rows = hs_max_rows[l];
+      a.hs_bytes = hs_bytes[l];
+    }
     const float* cache = fused ? a.qkv : tqkv;
     float* zf = fused ? trace->z + l * tstride : nullptr;  // the clean rows' hook_z (rows < Rc)
     if (use_lin[l]) {
@@ -2555,6 +2670,29 @@ int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32
                       (float*)(base + o_xf), (float*)(base + o_lg), trace->p_prob, trace->p_topk, trace->p_k,
                       nullptr, fmt, st));
   return TVR_OK;
+}
+
+int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32_t n_sites,
+                    const float* vectors, int32_t n_vectors, float* out_prob, int32_t* out_topk,
+                    int32_t topk, float* out_logits, void* stream) {
+  return sweep_impl("tvr_patch_sweep", m, trace, sites, n_sites, nullptr, nullptr, vectors, n_vectors, out_prob,
+                    out_topk, topk, out_logits, stream);
+}
+
+int tvr_patch_sweep_sets(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32_t n_sites,
+                         const int32_t* set_off, const tvr_head_patch* patches, const float* vectors,
+                         int32_t n_vectors, float* out_prob, int32_t* out_topk, int32_t topk, float* out_logits,
+                         void* stream) {
+  if (!m || !trace || !sites || n_sites <= 0 || !set_off)
+    return fail(TVR_ERR_INVALID, "tvr_patch_sweep_sets: bad argument");
+  if (set_off[0] < 0) return fail(TVR_ERR_INVALID, "tvr_patch_sweep_sets: set_off[0] is negative");
+  for (int i = 0; i < n_sites; ++i)
+    if (set_off[i + 1] < set_off[i])
+      return fail(TVR_ERR_INVALID, "tvr_patch_sweep_sets: set_off decreases at site " + std::to_string(i));
+  if (set_off[n_sites] > set_off[0] && !patches)
+    return fail(TVR_ERR_INVALID, "tvr_patch_sweep_sets: patches is null but the sets are not empty");
+  return sweep_impl("tvr_patch_sweep_sets", m, trace, sites, n_sites, set_off, patches, vectors, n_vectors, out_prob,
+                    out_topk, topk, out_logits, stream);
 }
 
 int tvr_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t gemm_mode, int32_t flags, int32_t* out) {

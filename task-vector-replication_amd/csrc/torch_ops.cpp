@@ -6,6 +6,7 @@
 //
 //   tvr::forward_clean   tvr_forward_clean / _deferred   (scratch2.py:96,143,183)
 //   tvr::patch_sweep     tvr_patch_sweep                 (scratch2.py:122-125,185-194)
+//   tvr::patch_sweep_sets tvr_patch_sweep_sets           (several scratch2.py:188 hooks in one run_with_hooks)
 //   tvr::project_heads   tvr_project_heads               (scratch2.py:97-98)
 //   tvr::forward_logits  tvr_forward_logits              (scratch.py:143,206,209)
 //
@@ -130,6 +131,43 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> patch_sweep(int64_t model, int64_
   return {prob, top, logits};
 }
 
+// patch_sweep with head-set sites (tvr_patch_sweep_sets).  set_off: CPU int32 [n_sites + 1]; patches: CPU
+// int32 [n_patches, 3] in tvr_head_patch field order (layer, head, vec).  vectors needs only float
+// alignment (an offset view is fine), so it is not required to be a fresh allocation — but contiguous.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> patch_sweep_sets(int64_t model, int64_t trace, const at::Tensor& sites,
+                                                                const at::Tensor& set_off, const at::Tensor& patches,
+                                                                const std::optional<at::Tensor>& vectors,
+                                                                int64_t topk, bool want_prob, bool want_logits,
+                                                                int64_t d_vocab, c10::Device device) {
+  static_assert(sizeof(tvr_site) == 9 * sizeof(int32_t), "tvr_site is 9 int32 fields");
+  static_assert(sizeof(tvr_head_patch) == 3 * sizeof(int32_t), "tvr_head_patch is 3 int32 fields");
+  TORCH_CHECK_VALUE(sites.dim() == 2 && sites.size(1) == 9, "tvr: sites must be [n_sites, 9] int32");
+  const int64_t n = sites.size(0);
+  TORCH_CHECK_VALUE(n > 0, "tvr: no patch sites");
+  TORCH_CHECK_VALUE(trace != 0, "tvr: patch_sweep_sets needs a trace");
+  TORCH_CHECK_VALUE(set_off.dim() == 1 && set_off.numel() == n + 1, "tvr: set_off must be [n_sites + 1] int32");
+  TORCH_CHECK_VALUE(patches.dim() == 2 && patches.size(1) == 3, "tvr: patches must be [n_patches, 3] int32");
+  const int32_t* off = host_i32(set_off, "set_off");
+  const int32_t* pat = host_i32(patches, "patches");
+  // the C ABI trusts set_off[n_sites] as the length of patches: check it against the tensor here
+  TORCH_CHECK_VALUE(off[0] >= 0 && off[n] <= patches.size(0), "tvr: set_off runs past patches (", off[n], " > ",
+                    patches.size(0), ") or starts below 0");
+  need_gpu(device);
+  DeviceGuard guard(device);
+  const float* vec = in_f32(vectors, device, "vectors");
+  const int32_t nvec = vectors.has_value() ? (int32_t)(vectors->numel() / std::max<int64_t>(vectors->size(-1), 1)) : 0;
+  auto prob = want_prob ? at::empty({n}, f32(device)) : at::empty({0}, f32(device));
+  auto top = at::empty({topk ? n : 0, topk}, at::TensorOptions().dtype(at::kInt).device(device));
+  auto logits = want_logits ? at::empty({n, d_vocab}, f32(device)) : at::empty({0}, f32(device));
+  check(tvr_patch_sweep_sets(as_model(model), reinterpret_cast<tvr_trace*>(static_cast<intptr_t>(trace)),
+                             reinterpret_cast<const tvr_site*>(host_i32(sites, "sites")), (int32_t)n, off,
+                             reinterpret_cast<const tvr_head_patch*>(pat), vec, nvec,
+                             want_prob ? prob.data_ptr<float>() : nullptr, topk ? top.data_ptr<int32_t>() : nullptr,
+                             (int32_t)topk, want_logits ? logits.data_ptr<float>() : nullptr, cur_stream(device)),
+        "tvr_patch_sweep_sets");
+  return {prob, top, logits};
+}
+
 // zsum [L, d] -> [L, H, d]
 at::Tensor project_heads(int64_t model, const at::Tensor& zsum, int64_t n_heads) {
   TORCH_CHECK_VALUE(zsum.dim() == 2, "tvr: zsum must be [n_layers, d_model]");
@@ -168,6 +206,8 @@ TORCH_LIBRARY(tvr, m) {
         "-> (Tensor, Tensor, Tensor, Tensor)");
   m.def("patch_sweep(int model, int trace, Tensor sites, Tensor? vectors, int topk, bool want_prob, "
         "bool want_logits, int d_vocab, Device device) -> (Tensor, Tensor, Tensor)");
+  m.def("patch_sweep_sets(int model, int trace, Tensor sites, Tensor set_off, Tensor patches, Tensor? vectors, "
+        "int topk, bool want_prob, bool want_logits, int d_vocab, Device device) -> (Tensor, Tensor, Tensor)");
   m.def("project_heads(int model, Tensor zsum, int n_heads) -> Tensor");
   m.def("forward_logits(int model, Tensor? tokens, Tensor? resid, int start_layer, Tensor seq_lens, int d_vocab, "
         "Device device) -> Tensor");
@@ -177,6 +217,7 @@ TORCH_LIBRARY(tvr, m) {
 TORCH_LIBRARY_IMPL(tvr, CompositeExplicitAutograd, m) {
   m.impl("forward_clean", &forward_clean);
   m.impl("patch_sweep", &patch_sweep);
+  m.impl("patch_sweep_sets", &patch_sweep_sets);
   m.impl("project_heads", &project_heads);
   m.impl("forward_logits", &forward_logits);
 }

@@ -16,6 +16,11 @@ patch-sweep launch sequence whose batch enumerates the sites:
   test_component_hypothesis                    scratch.py:106-147   (a12)
   substitute_task                              scratch.py:164-213
 
+Beyond the reference's loops (one run_with_hooks call with a scratch2.py:188
+hook per head of a set; the function-vector paper's joint mean-ablation):
+
+  joint_head_patch_effect, head_ablation_curve
+
 Drop-in notes
 * ``model`` is an ``amd.Model`` instead of a HookedTransformer; it must be
   passed (the reference's defaults bind a module-global model).
@@ -273,13 +278,27 @@ def calculate_average_causal_indirect_effect(mean_head_activations: torch.Tensor
 
 
 # ---------------------------------------------------------------- a10 / a11
+def _top_cie_index(causal_indirect_effects: torch.Tensor, layer: int, num_heads: int):
+    """Flat indices (l * H + h, torch.topk order and tie rule) of the
+    ``num_heads`` highest-CIE heads in layers ≤ ``layer``, and H: the head
+    selection ``assemble_task_vector`` and ``head_ablation_curve`` share."""
+    sub = causal_indirect_effects[: layer + 1, :]
+    _, idx = torch.topk(sub.flatten(), num_heads)
+    return idx, sub.shape[1]
+
+
+def top_cie_heads(causal_indirect_effects: torch.Tensor, layer: int, num_heads: int) -> List[Tuple[int, int]]:
+    """The (layer, head) pairs whose means ``assemble_task_vector(.., layer,
+    num_heads)`` sums, in its order."""
+    idx, H = _top_cie_index(causal_indirect_effects, layer, num_heads)
+    return [(int(i) // H, int(i) % H) for i in idx.tolist()]
+
+
 def assemble_task_vector(mean_head_activations: torch.Tensor, causal_indirect_effects: torch.Tensor,
                          layer: int, num_heads: int) -> torch.Tensor:
     """Sum of the mean outputs of the ``num_heads`` highest-CIE heads in
     layers ≤ ``layer`` (torch.topk order and tie rule, as the reference)."""
-    sub = causal_indirect_effects[: layer + 1, :]
-    _, idx = torch.topk(sub.flatten(), num_heads)
-    H = sub.shape[1]
+    idx, H = _top_cie_index(causal_indirect_effects, layer, num_heads)
     rows = mean_head_activations[(idx // H).to(mean_head_activations.device),
                                  (idx % H).to(mean_head_activations.device)]
     vec = torch.zeros(mean_head_activations.shape[-1], dtype=mean_head_activations.dtype,
@@ -472,3 +491,138 @@ def function_vector_head_count_grid(mean_head_activations: torch.Tensor, causal_
     for i, j, q in cells:
         acc[i, j] = float(hits[q]) / len(contexts)
     return acc
+
+
+# ------------------------------------------------------ joint head-set patching
+# Rows per patch_sweep_sets launch: an all-positions set site of a T-token
+# prompt holds T rows whatever its size (MAX_SITES_PER_LAUNCH CIE sites of 16
+# tokens: the workspace the CIE sweep already reaches).
+MAX_ROWS_PER_LAUNCH = 16 * MAX_SITES_PER_LAUNCH
+POSITION_KINDS = {"all": _lib.SITE_REPLACE_HEADSET_ALLPOS, "last": _lib.SITE_REPLACE_HEADSET_LASTPOS}
+
+
+def _check_head_sets(cfg, mean_head_activations, head_sets, n_prompts: int, n_answers: int, positions: str):
+    """Argument checks of the joint head-set functions (no engine call).
+    Returns the sets as lists of (layer, head) int pairs."""
+    if tuple(mean_head_activations.shape) != (cfg.n_layers, cfg.n_heads, cfg.d_model):
+        raise ValueError("Mean head activations must be of shape (n_layers, n_heads, d_model)")
+    if n_prompts != n_answers:
+        raise ValueError("Prompt answers must be of the same length as scrambled prompts")
+    if positions not in POSITION_KINDS:
+        raise ValueError(f"positions must be one of {sorted(POSITION_KINDS)}, got {positions!r}")
+    sets = []
+    for s in head_sets:
+        pairs = [(int(l), int(h)) for l, h in s]
+        if any(not (0 <= l < cfg.n_layers and 0 <= h < cfg.n_heads) for l, h in pairs):
+            raise ValueError("head set (layer, head) out of range")
+        if len(set(pairs)) != len(pairs):
+            raise ValueError("the same (layer, head) twice in one head set")
+        sets.append(pairs)
+    return sets
+
+
+@range_checked
+def joint_head_patch_effect(mean_head_activations: torch.Tensor, head_sets, scrambled_prompts, prompt_answers,
+                            model: Model = None, positions: str = "all", topk: int = 1) -> dict:
+    """Patch every head of a SET at once: for each set of ``head_sets`` (lists
+    of (layer, head)) and each prompt, one forward with
+    ``hook_result[0, :, h] = mean[l, h]`` (``positions="all"``, the reference's
+    hook, scratch2.py:188) or ``hook_result[0, -1, h] = mean[l, h]``
+    (``"last"``, the function-vector paper's) for every member (l, h), scoring
+    the first answer token (B3).  Prompts and answers as
+    ``calculate_average_causal_indirect_effect``.  Returns ``dprob`` [n_sets]
+    (mean over prompts of p_patched − p_clean, device), ``accuracy`` [n_sets]
+    (share of prompts whose answer token is in the patched top-``topk``),
+    ``clean_prob`` and ``clean_accuracy`` (floats).  Means of a corrupted task
+    give the joint mean-ablation of Todd et al. §3, means of the clean task
+    joint sufficiency.  One clean forward + one sweep per launch-sized group."""
+    cfg = model.cfg
+    sets = _check_head_sets(cfg, mean_head_activations, head_sets, len(scrambled_prompts), len(prompt_answers),
+                            positions)
+    if topk < 1:
+        raise ValueError("topk must be at least 1")
+    prompts, answers = normalize_cie_inputs(model, scrambled_prompts, prompt_answers)
+    L, H, dev = cfg.n_layers, cfg.n_heads, model.device
+    n_sets, n_prompts = len(sets), len(prompts)
+    if n_prompts == 0:
+        raise ValueError("no prompts")
+    vectors = mean_head_activations.to(dev, torch.float32).reshape(L * H, cfg.d_model).contiguous()
+    # one prompt's sets as (offsets, patches) relative to the prompt's first site
+    sizes = np.asarray([len(s) for s in sets], dtype=np.int64)
+    flat = np.asarray([(l, h, l * H + h) for s in sets for l, h in s], dtype=np.int32).reshape(-1, 3)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    maxT = max(len(p) for p in prompts)
+    rows_per_site = maxT if positions == "all" else 1
+    # chunk by rows, not only by sites: the sets of one launch, then the prompts of one launch
+    set_chunk = max(1, min(n_sets, MAX_SITES_PER_LAUNCH, MAX_ROWS_PER_LAUNCH // rows_per_site))
+    group = max(1, min(MAX_SITES_PER_LAUNCH, MAX_ROWS_PER_LAUNCH // rows_per_site) // max(min(n_sets, set_chunk), 1))
+    dsum = torch.zeros(n_sets, device=dev)
+    hits = torch.zeros(n_sets, device=dev)
+    clean_p = clean_hits = 0.0
+    for a, b in _chunks(n_prompts, group):
+        seqs = [list(map(int, p)) for p in prompts[a:b]]
+        tg = np.asarray(answers[a:b], dtype=np.int32)
+        n = len(seqs)
+        trace = model._sweep_trace(n, sum(len(s) for s in seqs))
+        clean = model.forward_clean(seqs, targets=tg.tolist(), topk=topk, trace=trace, defer=n_sets > 0)
+        tgd = torch.as_tensor(tg, device=dev)
+        for sa, sb in _chunks(n_sets, set_chunk):
+            m = sb - sa
+            sites = make_sites(n * m)
+            sites["seq"] = np.repeat(np.arange(n, dtype=np.int32), m)
+            sites["kind"] = POSITION_KINDS[positions]
+            sites["target"] = np.repeat(tg, m)
+            lens = np.tile(sizes[sa:sb], n)
+            off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+            pat = np.tile(flat[starts[sa]:starts[sb]], (n, 1))
+            out = model.patch_sweep_sets(trace, sites, off, pat, vectors, topk=topk)
+            p = out["prob"].view(n, m)
+            dsum[sa:sb] += (p - clean["prob"][:, None]).sum(0)
+            hits[sa:sb] += (out["topk"].view(n, m, topk) == tgd[:, None, None]).any(-1).sum(0)
+        # (the deferred clean outputs are written by the group's first sweep; without sets the forward ran at once)
+        clean_p += float(clean["prob"].sum())
+        clean_hits += float((clean["topk"] == tgd[:, None]).any(-1).sum())
+    return {"dprob": dsum / n_prompts, "accuracy": hits / n_prompts, "clean_prob": clean_p / n_prompts,
+            "clean_accuracy": clean_hits / n_prompts}
+
+
+@range_checked
+def head_ablation_curve(mean_head_activations: torch.Tensor, causal_indirect_effects: torch.Tensor,
+                        scrambled_prompts, prompt_answers, model: Model = None,
+                        counts: Sequence[int] = (1, 2, 5, 10, 20), layer: Optional[int] = None, n_random: int = 0,
+                        seed: int = 0, positions: str = "all", topk: int = 1) -> dict:
+    """For each k of ``counts``: jointly patch the k highest-CIE heads of
+    layers ≤ ``layer`` (default: every layer; ``assemble_task_vector``'s
+    selection and tie order) with their rows of ``mean_head_activations``, and
+    ``n_random`` control sets of k heads drawn from the same layers with
+    ``random.Random(seed)`` (for each k in turn, ``n_random`` calls of
+    ``sample(all (l, h) of those layers in row-major order, k)``).  Means of a
+    corrupted or unrelated task give the ablation curve of Todd et al. §3,
+    means of the clean task joint sufficiency.  Returns ``counts``, ``heads``
+    (the top-k list per k), ``random_heads`` (per k, ``n_random`` lists),
+    ``top`` (``dprob`` / ``accuracy`` [len(counts)]), ``random`` (the same,
+    [len(counts), n_random]), ``clean_prob`` and ``clean_accuracy``: all from
+    ONE ``joint_head_patch_effect`` call."""
+    cfg = model.cfg
+    layer = cfg.n_layers - 1 if layer is None else int(layer)
+    if not 0 <= layer < cfg.n_layers:
+        raise ValueError("layer out of range")
+    if tuple(causal_indirect_effects.shape) != (cfg.n_layers, cfg.n_heads):
+        raise ValueError("Causal indirect effects must be of shape (n_layers, n_heads)")
+    counts = [int(k) for k in counts]
+    pool = [(l, h) for l in range(layer + 1) for h in range(cfg.n_heads)]
+    if any(k < 1 or k > len(pool) for k in counts):
+        raise ValueError("every count must be between 1 and the number of heads in layers <= layer")
+    if n_random < 0:
+        raise ValueError("n_random must not be negative")
+    rng = random.Random(seed)
+    heads = [top_cie_heads(causal_indirect_effects, layer, k) for k in counts]
+    random_heads = [[rng.sample(pool, k) for _ in range(n_random)] for k in counts]
+    sets = heads + [s for per_k in random_heads for s in per_k]
+    r = joint_head_patch_effect(mean_head_activations, sets, scrambled_prompts, prompt_answers, model=model,
+                                positions=positions, topk=topk)
+    nk = len(counts)
+    return {"counts": counts, "heads": heads, "random_heads": random_heads,
+            "top": {"dprob": r["dprob"][:nk], "accuracy": r["accuracy"][:nk]},
+            "random": {"dprob": r["dprob"][nk:].view(nk, n_random), "accuracy": r["accuracy"][nk:].view(nk, n_random)},
+            "clean_prob": r["clean_prob"], "clean_accuracy": r["clean_accuracy"]}

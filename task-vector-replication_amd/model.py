@@ -475,6 +475,44 @@ class Model(TokenizerMixin):
             out["logits"] = logits
         return out
 
+    def patch_sweep_sets(self, trace: Trace, sites: np.ndarray, set_off, patches,
+                         vectors: Optional[torch.Tensor] = None, topk: int = 0, want_prob: bool = True,
+                         return_logits: bool = False) -> Dict[str, torch.Tensor]:
+        """``patch_sweep`` with joint head-set sites (tvr_patch_sweep_sets): site
+        ``i`` of kind ``SITE_REPLACE_HEADSET_ALLPOS`` / ``_LASTPOS`` replaces
+        ``hook_result`` of every ``(layer, head)`` of ``patches[set_off[i]:set_off[i+1]]``
+        (rows ``(layer, head, vec)``) by ``vectors[vec]``, at every position or at
+        the last one; sites of the other kinds own an empty range and behave as
+        in ``patch_sweep``.  Returns the same dictionary."""
+        sites = np.ascontiguousarray(sites, dtype=SITE_DTYPE)
+        n = int(sites.shape[0])
+        if n == 0:
+            raise ValueError("no patch sites")
+        off = np.ascontiguousarray(set_off, dtype=np.int32).reshape(-1)
+        pat = np.ascontiguousarray(patches, dtype=np.int32).reshape(-1, 3)
+        if off.shape[0] != n + 1:
+            raise ValueError("set_off must have n_sites + 1 entries")
+        if off[0] < 0 or np.any(np.diff(off) < 0) or off[-1] > pat.shape[0]:
+            raise ValueError("set_off must be non-decreasing and stay inside patches")
+        if vectors is not None:
+            if vectors.device != self.device or vectors.dtype != torch.float32:
+                raise ValueError("vectors must be fp32 on the model device")
+            vectors = vectors.reshape(-1, self.cfg.d_model).contiguous()
+        rows = torch.from_numpy(sites.view(np.int32).reshape(n, len(_lib.SITE_FIELDS)))
+        prob, top, logits = self._op("patch_sweep_sets", self._h.value, trace._h.value, rows, torch.from_numpy(off),
+                                     torch.from_numpy(pat), vectors, topk, want_prob, return_logits,
+                                     self.cfg.d_vocab, self.device)
+        self._check_range("tvr_patch_sweep_sets")
+        trace._pending_out = None
+        out = {}
+        if want_prob:
+            out["prob"] = prob
+        if topk:
+            out["topk"] = top
+        if return_logits:
+            out["logits"] = logits
+        return out
+
     def project_heads(self, zsum: torch.Tensor) -> torch.Tensor:
         """[L, d] z-sums → [L, H, d] hook_result sums."""
         if tuple(zsum.shape) != (self.cfg.n_layers, self.cfg.d_model):
