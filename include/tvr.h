@@ -346,12 +346,21 @@ int tvr_gemm_x2f16(const float* A, int32_t lda, const uint16_t* W, int32_t ldw,
 /* The activation format the engine's producers write for every GEMM input in
  * a planar mode: logical [rows][K] -> halves [rows][2][K]; X2F16: plane 0 =
  * fp16(16 a), plane 1 = fp16(16 a - plane 0), *range_flag (may be NULL) |= 1
- * if |a| >= 4095; BF16: plane 0 = bf16(a). */
+ * if |a| >= 4095; BF16: plane 0 = bf16(a).
+ * fmt = TVR_ACT_X2F16_IL (K % 32 == 0): the X2F16 values in the k-tile-
+ * interleaved layout the exact-fp16 sweeps use internally, halves
+ * [rows][K / 32][2][32] — per row and 32-column group, 64 B of plane 0 then
+ * 64 B of plane 1 (one 128-B line): column c of plane p is half
+ * (c / 32) * 64 + p * 32 + c % 32 of the row.  Same values, same bytes per
+ * row (2 K halves), same range flag. */
+#define TVR_ACT_X2F16_IL 0x12 /* TVR_GEMM_X2F16 | 0x10 */
 int tvr_act_rows(int32_t fmt, const float* a, int32_t lda, uint16_t* out, int32_t rows,
                  int32_t K, uint32_t* range_flag, void* stream);
 /* The engine's planar GEMM: A in the activation format above (lda logical
  * elements per row, >= K), W planes from tvr_weight_planes (w_scale: the
- * X2F16 scale, 1 for BF16). */
+ * X2F16 scale, 1 for BF16).  fmt = TVR_ACT_X2F16_IL: A in the interleaved
+ * layout (row stride 2 lda halves), the X2F16 weight planes; the same
+ * products in the same order as TVR_GEMM_X2F16 — bitwise the same C. */
 int tvr_gemm_planar(int32_t fmt, const uint16_t* A, int32_t lda, const uint16_t* W,
                     int32_t ldw, size_t wps, float w_scale, const float* bias,
                     float* C, int32_t ldc, int32_t M, int32_t N, int32_t K,

@@ -409,7 +409,7 @@ attention_mfma_kernel(const float* __restrict__ qkv, int ldq, const float* __res
         const int col = h * DH + 8 * c;
         if constexpr (FMT != ACT_F32) {
           const float v8[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-          store_act8<FMT>((uint16_t*)z + zrow * 2 * ldz + col, ldz, v8, flag);
+          store_act8<FMT>((uint16_t*)z + zrow * 2 * ldz + act_col<FMT>(col), act_ps<FMT>(ldz), v8, flag);
         } else {
           *(f4*)((float*)z + zrow * ldz + col) = a;
           *(f4*)((float*)z + zrow * ldz + col + 4) = b;
@@ -429,7 +429,7 @@ attention_mfma_kernel(const float* __restrict__ qkv, int ldq, const float* __res
         const int col = h * DH + zcol(c);
         const f4 v = zgroup(c);
         if constexpr (FMT != ACT_F32)
-          store_act4<FMT>((uint16_t*)z + zrow * 2 * ldz + col, ldz, v[0], v[1], v[2], v[3], flag);
+          store_act4<FMT>((uint16_t*)z + zrow * 2 * ldz + act_col<FMT>(col), act_ps<FMT>(ldz), v[0], v[1], v[2], v[3], flag);
         else
           *(f4*)((float*)z + zrow * ldz + col) = v;
         if (zf && !zf_last && zrow < (size_t)zf_rows) *(f4*)(zf + zrow * ldzf + col) = v;
@@ -553,7 +553,7 @@ attention_row_kernel(const float* __restrict__ qkv, int ldq, const float* __rest
   for (int c = 4 * lane; c < HG * DH; c += 256) {
     const f32x4 v = *(const f32x4*)(zw + c);
     if constexpr (FMT != ACT_F32)
-      store_act4<FMT>((uint16_t*)z + zrow * 2 * ldz + c0 + c, ldz, v[0], v[1], v[2], v[3], flag);
+      store_act4<FMT>((uint16_t*)z + zrow * 2 * ldz + act_col<FMT>(c0 + c), act_ps<FMT>(ldz), v[0], v[1], v[2], v[3], flag);
     else
       *(f32x4u*)((float*)z + zrow * ldz + c0 + c) = v;
     if (zf && zf_last) *(f32x4u*)(zf + (size_t)s * ldzf + c0 + c) = v;  // the capture's compact last-row copy

@@ -160,6 +160,9 @@ struct tvr_model {
   // constant to every element of a row's residual, which every LayerNorm (and the centred trace export)
   // removes.  Both then run 2 MFMA products per slice instead of 3 (gemm_pingpong.hpp WX).
   bool x16 = false;
+  // the exact-fp16 sweeps' GEMM inputs (xn, xn2, a2, xf) in the k-tile-interleaved layout (ACT_X2F16I, split.hpp);
+  // false (TVR_ACT_LAYOUT=planar, read when the GEMM mode is set): the planar [rows][2][K] layout
+  bool act_il = true;
   std::vector<MatW> w1x, w2x;
   std::vector<const float*> g1, g2;
   // the unembed's raw W_U [V][d] (one fp16 plane) and the final LN's gamma (tvr_model_set_exact16_unembed): the
@@ -335,6 +338,15 @@ int act_fmt(const tvr_model* m) {
 // the exact-fp16 weight path (tvr_model_set_exact16) is on: x2f16 mode with the raw planes attached
 bool use_x16(const tvr_model* m) { return m->x16 && m->gemm_mode == TVR_GEMM_X2F16; }
 
+// TVR_ACT_LAYOUT=planar keeps the exact-fp16 sweeps' GEMM inputs in the planar layout (A/B runs, tests)
+bool act_layout_interleaved() {
+  const char* e = getenv("TVR_ACT_LAYOUT");
+  return !(e && std::string(e) == "planar");
+}
+// Format of the sweep buffers xn, xn2, a2 and xf (Acts::fmt): on the exact-fp16 path the interleaved layout,
+// which only the one-plane GEMM reads; the side buffers (vact, vg, G) keep act_fmt's planar layout.
+int acts_fmt(const tvr_model* m) { return use_x16(m) && m->act_il ? (int)ACT_X2F16I : act_fmt(m); }
+
 // gemm_pingpong_kernel over tiles [tile_base, tile_base + count) of a planar
 // launch's raster (count 0: all), VEC epilogue
 // Raster group (m-blocks walked before the next block column): 4, or 2 when
@@ -351,8 +363,10 @@ int pp_group_m(int N) {
   return (N + 255) / 256 <= 16 ? small : large;
 }
 
+// ail: A in the interleaved x2f16 layout (a_fmt ACT_X2F16; launch_gemm checks the combinations)
 void launch_pp(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, int ldw, int M, int N, int K,
-               const GemmEpi& ep0, float acc_scale, int tile_base, int count, bool vec, bool sl, hipStream_t st) {
+               const GemmEpi& ep0, float acc_scale, int tile_base, int count, bool vec, bool sl, hipStream_t st,
+               bool ail = false) {
   GemmEpi ep = ep0;
   ep.tile_base = tile_base;
   ep.tile_count = count;
@@ -376,6 +390,32 @@ void launch_pp(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, i
   }
   if (a_fmt == ACT_F16) {  // the bf16 mode's Q / K columns: plain fp32 outputs only (launch_gemm checks)
     TVR_PP1V(EPI_BIAS, ACT_F16, false, false);
+    return;
+  }
+  if (ail) {  // one-plane weights: every epilogue; two weight planes (the primitive ABI entry point): EPI_BIAS
+#define TVR_PPI(E, V, S, X)                                                                                          \
+  hipLaunchKernelGGL((gemm_pingpong_kernel<E, ACT_X2F16, V, 0, false, S, X, true>), g, dim3(PP_THREADS), 0, st, Ah, \
+                     2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, ep)
+#define TVR_PPIV(E, X)                                                             \
+  if (vec) {                                                                       \
+    if (sl) { TVR_PPI(E, true, true, X); } else { TVR_PPI(E, true, false, X); }    \
+  } else {                                                                         \
+    if (sl) { TVR_PPI(E, false, true, X); } else { TVR_PPI(E, false, false, X); }  \
+  }
+    if (!wx) {
+      TVR_PPIV(EPI_BIAS, false);
+    } else {
+      switch (epi) {
+        case EPI_BIAS: TVR_PPIV(EPI_BIAS, true); break;
+        case EPI_SPLIT_GELU_ACT: TVR_PPIV(EPI_SPLIT_GELU_ACT, true); break;
+        case EPI_STATS:
+          if (sl) { TVR_PPI(EPI_STATS, true, true, true); } else { TVR_PPI(EPI_STATS, true, false, true); }
+          break;
+        default: TVR_PPIV(EPI_RESID, true); break;
+      }
+    }
+#undef TVR_PPIV
+#undef TVR_PPI
     return;
   }
   switch (epi) {
@@ -402,7 +442,7 @@ void launch_pp(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, i
 // in order and applies the epilogue (deterministic).
 int launch_pp_splitk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, int ldw, int M, int N, int K,
                      const GemmEpi& ep0, float acc_scale, int tile_base, int count, int ksplit, bool sl, tvr_model* m,
-                     hipStream_t st) {
+                     hipStream_t st, bool ail = false) {
   const int rc = ensure_splitk(m, (size_t)ksplit * count * PP_TILE_ELEMS * sizeof(float), st);
   if (rc != TVR_OK) return rc;
   GemmEpi ep = ep0;  // the reduce's epilogue: same raster as the partial launch
@@ -418,7 +458,13 @@ int launch_pp_splitk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW
   pe.a2 = ep.a2;  // the exact-fp16 QKV + MLP-in launch's second A operand (by column)
   pe.a2_col = ep.a2_col;
   const bool wx = a_fmt == ACT_X2F16 && W.x16;
-  if (a_fmt == ACT_X2F16 && wx && sl)
+  if (ail && sl)  // (one-plane weights: launch_gemm checks)
+    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, true, true, true>), g,
+                       dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
+  else if (ail)
+    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, false, true, true>), g,
+                       dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
+  else if (a_fmt == ACT_X2F16 && wx && sl)
     hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, true, true>), g, dim3(PP_THREADS), 0,
                        st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
   else if (a_fmt == ACT_X2F16 && wx)
@@ -439,8 +485,10 @@ int launch_pp_splitk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW
 #define TVR_SK_REDUCE(E, F)                                                                                     \
   hipLaunchKernelGGL((splitk_reduce_kernel<E, F>), rg, dim3(256), 0, st, (const float*)m->splitk_ws, ksplit, \
                      tile_base, count, M, N, ep)
-#define TVR_SK_REDUCE_F(E) \
-  if (a_fmt == ACT_X2F16) { TVR_SK_REDUCE(E, ACT_X2F16); } else { TVR_SK_REDUCE(E, ACT_BF16); }
+#define TVR_SK_REDUCE_F(E)                                          \
+  if (ail) { TVR_SK_REDUCE(E, ACT_X2F16I); }                        \
+  else if (a_fmt == ACT_X2F16) { TVR_SK_REDUCE(E, ACT_X2F16); }     \
+  else { TVR_SK_REDUCE(E, ACT_BF16); }
   switch (epi) {
     case EPI_BIAS: TVR_SK_REDUCE_F(EPI_BIAS); break;
     case EPI_SPLIT_GELU_ACT: TVR_SK_REDUCE_F(EPI_SPLIT_GELU_ACT); break;
@@ -457,7 +505,7 @@ int launch_pp_splitk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW
 // partials in k order and applies the epilogue (deterministic).
 int launch_pp_sk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, int ldw, int M, int N, int K,
                  const GemmEpi& ep0, float acc_scale, int tile_base, int count, int G, bool sl, tvr_model* m,
-                 hipStream_t st) {
+                 hipStream_t st, bool ail = false) {
   const int rc = ensure_splitk(m, (size_t)2 * G * PP_TILE_ELEMS * sizeof(float), st);
   if (rc != TVR_OK) return rc;
   GemmEpi ep = ep0;
@@ -473,7 +521,13 @@ int launch_pp_sk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W,
   pe.a2 = ep.a2;
   pe.a2_col = ep.a2_col;
   const bool wx = a_fmt == ACT_X2F16 && W.x16;
-  if (a_fmt == ACT_X2F16 && wx && sl)
+  if (ail && sl)  // (one-plane weights: launch_gemm checks)
+    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true, true, true, true>), g,
+                       dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
+  else if (ail)
+    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true, false, true, true>), g,
+                       dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
+  else if (a_fmt == ACT_X2F16 && wx && sl)
     hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true, true, true>), g, dim3(PP_THREADS), 0, st,
                        Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
   else if (a_fmt == ACT_X2F16 && wx)
@@ -495,8 +549,10 @@ int launch_pp_sk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W,
 #define TVR_SKR(E, F)                                                                                         \
   hipLaunchKernelGGL((splitk_sk_reduce_kernel<E, F>), rg, dim3(256), 0, st, (const float*)m->splitk_ws, G, KT, \
                      tile_base, count, M, N, ep)
-#define TVR_SKR_F(E) \
-  if (a_fmt == ACT_X2F16) { TVR_SKR(E, ACT_X2F16); } else { TVR_SKR(E, ACT_BF16); }
+#define TVR_SKR_F(E)                                     \
+  if (ail) { TVR_SKR(E, ACT_X2F16I); }                   \
+  else if (a_fmt == ACT_X2F16) { TVR_SKR(E, ACT_X2F16); } \
+  else { TVR_SKR(E, ACT_BF16); }
   switch (epi) {
     case EPI_BIAS: TVR_SKR_F(EPI_BIAS); break;
     case EPI_SPLIT_GELU_ACT: TVR_SKR_F(EPI_SPLIT_GELU_ACT); break;
@@ -675,6 +731,14 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
                 int K, const GemmEpi& ep, hipStream_t st, tvr_model* m = nullptr,
                 unsigned* range_flag = nullptr) {
   if (M <= 0 || N <= 0) return TVR_OK;
+  // ACT_X2F16I: x2f16 values, A's addresses interleaved (ail); the kernels' FMT stays ACT_X2F16.  The one-plane
+  // GEMM takes every epilogue and plan, two weight planes the plain EPI_BIAS launch only (no model, no plan).
+  const bool ail = a_fmt == ACT_X2F16I;
+  if (ail) {
+    a_fmt = ACT_X2F16;
+    if (!W.x16 && (epi != EPI_BIAS || m || ep.skinny))
+      return fail(TVR_ERR_INVALID, "gemm: the interleaved activation layout belongs to the one-plane exact-fp16 GEMMs");
+  }
   const bool planar = a_fmt != ACT_F32;
   if (planar && !W.h) return fail(TVR_ERR_INVALID, "gemm: planar activations need the planar weight planes");
   if (epi == EPI_SPLIT_GELU_ACT && !planar)
@@ -713,7 +777,7 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
     const bool sl = a_fmt == ACT_X2F16 && (K >= PP_SLICE_MIN_K || (m && m->K2 >= PP_SLICE_MIN_K)) &&
                     (!W.x16 || wx_slice == 1 || (wx_slice == 2 && epi == EPI_RESID));
     if (ep.skinny && epi == EPI_BIAS && M <= SK_USE_M && !ep.out_rows && ep.k_split <= 1 && vec &&
-        a_fmt != ACT_F16 && !W.x16 && !ep.a2) {
+        a_fmt != ACT_F16 && !W.x16 && !ep.a2 && !ail) {
       // a few rows (the linearised entry's G on a rank of a head split): gemm_skinny.hpp
       const dim3 g(gemm_skinny_grid(N));
 #define TVR_SK(F, MT)                                                                                  \
@@ -734,18 +798,18 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
       if (m && vec && epi != EPI_STATS) plan = plan_pp_cached(m, M, N, K, a_fmt, epi, a_fmt == ACT_X2F16 && W.x16);
       if (plan.sk_base >= 0) {
         if (plan.sk_base > 0)
-          launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, plan.sk_base, true, sl, st);
+          launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, plan.sk_base, true, sl, st, ail);
         TVR_TRY(launch_pp_sk(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, plan.sk_base,
-                             gemm_pingpong_grid(M, N) - plan.sk_base, plan.sk_blocks, sl, m, st));
+                             gemm_pingpong_grid(M, N) - plan.sk_base, plan.sk_blocks, sl, m, st, ail));
       } else if (plan.ksplit > 1) {
         TVR_TRY(launch_pp_splitk(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, gemm_pingpong_grid(M, N),
-                                 plan.ksplit, sl, m, st));
+                                 plan.ksplit, sl, m, st, ail));
       } else if (plan.tail_base > 0) {
-        launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, plan.tail_base, true, sl, st);
+        launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, plan.tail_base, true, sl, st, ail);
         TVR_TRY(launch_pp_splitk(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, plan.tail_base,
-                                 gemm_pingpong_grid(M, N) - plan.tail_base, plan.tail_split, sl, m, st));
+                                 gemm_pingpong_grid(M, N) - plan.tail_base, plan.tail_split, sl, m, st, ail));
       } else {
-        launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, 0, vec, sl, st);
+        launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, 0, vec, sl, st, ail);
       }
     }
   } else {
@@ -943,7 +1007,7 @@ int launch_lnpre(const float* x, int ldx, const int32_t* idx, void* y, int ldy, 
   ProfSpan ps(m, st);
   if (d % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0)
     return fail(TVR_ERR_UNSUPPORTED, "lnpre: d and strides must be multiples of 4");
-  if (g1 && (fmt != ACT_X2F16 || (y2 && !g2) || !m))
+  if (g1 && (!act_is_x2(fmt) || (y2 && !g2) || !m))
     return fail(TVR_ERR_INTERNAL, "lnpre: the gamma-scaled rows are an x2f16 model path");
   const int rows_per_block = 4;
   const dim3 grid((rows + rows_per_block - 1) / rows_per_block), block(64 * rows_per_block);
@@ -961,6 +1025,8 @@ int launch_lnpre(const float* x, int ldx, const int32_t* idx, void* y, int ldy, 
   }
   if (fmt == ACT_X2F16) {
     TVR_LNPRE_NV(ACT_X2F16, g1, g2, y2, m ? m->range_flag : nullptr);
+  } else if (fmt == ACT_X2F16I) {
+    TVR_LNPRE_NV(ACT_X2F16I, g1, g2, y2, m ? m->range_flag : nullptr);
   } else if (fmt == ACT_BF16) {
     TVR_LNPRE_NV(ACT_BF16, nullptr, nullptr, nullptr, nullptr);
   } else {
@@ -1032,6 +1098,8 @@ int launch_attention(tvr_model* m, const float* qkv, const float* cache_qkv, con
   else if (dh == 80) { TVR_ATTR(F, 80); } else { TVR_ATTR(F, 128); }
     if (fmt == ACT_X2F16) {
       TVR_ATTR_DH(ACT_X2F16);
+    } else if (fmt == ACT_X2F16I) {
+      TVR_ATTR_DH(ACT_X2F16I);
     } else if (fmt == ACT_BF16) {
       TVR_ATTR_DH(ACT_BF16);
     } else {
@@ -1071,6 +1139,8 @@ int launch_attention(tvr_model* m, const float* qkv, const float* cache_qkv, con
   else if (dh == 80) { TVR_ATTM_NK(F, 80); } else { TVR_ATTM_NK(F, 128); }
   if (fmt == ACT_X2F16) {
     TVR_ATTM_DH(ACT_X2F16);
+  } else if (fmt == ACT_X2F16I) {
+    TVR_ATTM_DH(ACT_X2F16I);
   } else if (fmt == ACT_BF16) {
     TVR_ATTM_DH(ACT_BF16);
   } else {
@@ -1099,7 +1169,7 @@ GemmEpi epi_qkv_mlpin(tvr_model* m, const float* b1, float* qkv, const Acts& a) 
   e.out0m = a.qkv_mirror;
   e.mirror_rows = a.mirror_rows;
   if (planar) {
-    e.out1h = reinterpret_cast<uint16_t*>(a.a2) + d;
+    e.out1h = reinterpret_cast<uint16_t*>(a.a2) + act_col_rt(a.fmt, d);  // (the kernels map the columns after it)
     e.ld1h = 2 * m->K2;
     e.ps1h = m->K2;
     e.range_flag = m->range_flag;
@@ -1130,10 +1200,10 @@ double attention_bytes(int d, int q_rows, int kv_rows, int fmt, int zf_rows) {
 int launch_w1(tvr_model* m, int l, const void* xn, int M, int c0, int N, const GemmEpi& ep, hipStream_t st,
               const void* xn2 = nullptr) {
   const int d = m->cfg.d_model;
-  const int fmt = act_fmt(m);
+  const int fmt = xn2 ? acts_fmt(m) : act_fmt(m);  // (the gamma-scaled pair: the sweep buffers xn / xn2)
   const int epi = fmt != ACT_F32 ? EPI_SPLIT_GELU_ACT : EPI_SPLIT_GELU;
   if (xn2) {
-    if (!use_x16(m) || fmt != ACT_X2F16) return fail(TVR_ERR_INTERNAL, "launch_w1: gamma-scaled rows off the x16 path");
+    if (!use_x16(m) || !act_is_x2(fmt)) return fail(TVR_ERR_INTERNAL, "launch_w1: gamma-scaled rows off the x16 path");
     const MatW W = m->w1x[l].rows((size_t)c0 * d);
     const int qkv_end = 3 * d - c0;  // first column of the launch that reads xn2
     if (qkv_end <= 0)
@@ -1192,17 +1262,18 @@ int apply_headset(tvr_model* m, const Acts& a, hipStream_t st) {
   const bool planar = a.fmt != ACT_F32;
   const size_t row_bytes = (size_t)m->K2 * 4;  // fp32 [K2], or halves [2][K2]
   const int slice_bytes = c.d_head * (planar ? 2 : 4);
-  const int n_planes = a.fmt == ACT_X2F16 ? 2 : 1;
+  const int n_planes = act_is_x2(a.fmt) ? 2 : 1;
+  const int il = a.fmt == ACT_X2F16I;
   const size_t plane_bytes = (size_t)m->K2 * 2;
   const dim3 g(a.hs_n, (a.hs_max_rows + HEADSET_ROWS - 1) / HEADSET_ROWS);
   const bool v4 = ((uintptr_t)a.hs_vectors & 15) == 0 && d % 4 == 0;
   ProfSpan ps(m, st);
   if (v4)
     hipLaunchKernelGGL(headset_patch_kernel<true>, g, dim3(HEADSET_THREADS), 0, st, a.hs_items, a.hs_patches,
-                       a.hs_vectors, (char*)a.a2, row_bytes, slice_bytes, n_planes, plane_bytes, a.resid, d);
+                       a.hs_vectors, (char*)a.a2, row_bytes, slice_bytes, n_planes, plane_bytes, a.resid, d, il);
   else
     hipLaunchKernelGGL(headset_patch_kernel<false>, g, dim3(HEADSET_THREADS), 0, st, a.hs_items, a.hs_patches,
-                       a.hs_vectors, (char*)a.a2, row_bytes, slice_bytes, n_planes, plane_bytes, a.resid, d);
+                       a.hs_vectors, (char*)a.a2, row_bytes, slice_bytes, n_planes, plane_bytes, a.resid, d, il);
   TVR_HIP(hipGetLastError());
   ps.done(TVR_HBM_ENTRY, a.hs_bytes);
   return TVR_OK;
@@ -1319,6 +1390,7 @@ int run_final(tvr_model* m, const float* resid, const int32_t* d_rows, const int
     // the exact-fp16 unembed: LNPre(x) o gamma_f against the raw W_U (the statistics are invariant to the
     // per-row constant this leaves in the logits; the logits path removes it below)
     const bool xu = use_x16(m) && m->wux.h;
+    if (xu) fmt = acts_fmt(m);  // xf: read by the one-plane unembed
     TVR_TRY(launch_lnpre(resid, d, d_rows + s, xf, d, cn, d, c.ln_eps, fmt, st, m, nullptr, nullptr, 0,
                          xu ? m->gf : nullptr));
     if (fused) {
@@ -1672,6 +1744,7 @@ int tvr_model_set_gemm(tvr_model* m, int32_t mode, void* stream) {
   TVR_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(unsigned), st));
   TVR_HIP(hipStreamSynchronize(st));
   m->gemm_mode = mode;
+  m->act_il = act_layout_interleaved();
   return TVR_OK;
 }
 
@@ -1934,7 +2007,7 @@ int forward_impl(tvr_model* m, tvr_trace* trace, const int32_t* tokens, const fl
 
   const int fmt = act_fmt(m);
   Acts a{(float*)(base + o_resid), (float*)(base + o_xn), trace ? nullptr : (float*)(base + o_qkv),
-         (float*)(base + o_a2), fmt};
+         (float*)(base + o_a2), acts_fmt(m)};
   if (use_x16(m)) a.xn2 = (float*)(base + o_xn2);
   const SeqDesc* d_seqs = (const SeqDesc*)(base + o_seqs);
   const int32_t* d_last = (const int32_t*)(base + o_last);
@@ -2455,7 +2528,7 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
 
   const int fmt = act_fmt(m);
   Acts a{(float*)(base + o_resid), (float*)(base + o_xn), (float*)(base + o_qkv),
-         (float*)(base + o_a2), fmt};
+         (float*)(base + o_a2), acts_fmt(m)};
   if (use_x16(m)) a.xn2 = (float*)(base + o_xn2);
   const SeqDesc* d_seqs = (const SeqDesc*)(base + o_seqs);
   const EntryDesc* d_ents = (const EntryDesc*)(base + o_ents);
@@ -2525,7 +2598,7 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
   auto run_block_lin = [&](int l, int Rl, const float* cache, float* zf) -> int {
     const tvr_layer_weights& w = m->layers[l];
     const int Rp = Rc + rows_le[l - 1], D1 = m->D1;
-    TVR_TRY(launch_lnpre(a.resid, d, nullptr, a.xn, d, Rl, d, c.ln_eps, fmt, st, m, lnstats, a.resid_mirror,
+    TVR_TRY(launch_lnpre(a.resid, d, nullptr, a.xn, d, Rl, d, c.ln_eps, a.fmt, st, m, lnstats, a.resid_mirror,
                          a.mirror_rows, a.xn2 ? m->g1[l] : nullptr, a.xn2 ? m->g2[l] : nullptr, a.xn2));
     GemmEpi e1 = epi_qkv_mlpin(m, w.b1, a.qkv, a);
     e1.raw = raw_h;
@@ -2585,18 +2658,21 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
     float acc_scale = fmt == ACT_X2F16 ? 1.0f / (m->lin_scale[l] * X2_ASCALE) : 1.0f;
     dim3 g;
     int ct_base = 0;
-#define TVR_LIN(F, NK)                                                                                             \
-  hipLaunchKernelGGL((lin_entry_kernel<F, NK>), g, dim3(LIN_THREADS), 0, st,                                       \
+#define TVR_LIN(F, NK, ...)                                                                                        \
+  hipLaunchKernelGGL((lin_entry_kernel<F, NK __VA_OPT__(,) __VA_ARGS__>), g, dim3(LIN_THREADS), 0, st,              \
                      (const LinMB*)(base + o_lin_mbs) + lin_mb_off[l], lin_nmb[l], (const LinRow*)(base + o_lin_rows), \
                      wp, per, acc_scale, trace->z + (size_t)(l - 1) * tstride, d, c.d_head, lnstats, a.qkv, raw_h,     \
                      c.d_mlp, (const float*)(base + o_g), m->lin_c1 + (size_t)l * D1, w.b1, D1,                         \
-                     reinterpret_cast<uint16_t*>(a.a2) + d, 2 * m->K2, m->K2, m->range_flag, ct_base)
-#define TVR_LIN_K(F)                                                      \
-  if (KP == 32) TVR_LIN(F, 1);                                            \
-  else if (KP == 64) TVR_LIN(F, 2);                                       \
-  else if (KP == 96) TVR_LIN(F, 3);                                       \
-  else TVR_LIN(F, 4)
-    if (fmt == ACT_X2F16) {
+                     reinterpret_cast<uint16_t*>(a.a2) + act_col_rt(a.fmt, d), 2 * m->K2, m->K2, m->range_flag, ct_base)
+#define TVR_LIN_K(F, ...)                                                 \
+  if (KP == 32) TVR_LIN(F, 1 __VA_OPT__(,) __VA_ARGS__);                  \
+  else if (KP == 64) TVR_LIN(F, 2 __VA_OPT__(,) __VA_ARGS__);             \
+  else if (KP == 96) TVR_LIN(F, 3 __VA_OPT__(,) __VA_ARGS__);             \
+  else TVR_LIN(F, 4 __VA_OPT__(,) __VA_ARGS__)
+    if (fmt == ACT_X2F16 && a.fmt == ACT_X2F16I) {  // a2's GELU planes interleaved
+      g = dim3(lin_nmb[l] * n_ct);
+      TVR_LIN_K(ACT_X2F16, true);
+    } else if (fmt == ACT_X2F16) {
       g = dim3(lin_nmb[l] * n_ct);
       TVR_LIN_K(ACT_X2F16);
     } else {
@@ -2781,13 +2857,17 @@ int tvr_gemm_x2f16(const float* A, int32_t lda, const uint16_t* W, int32_t ldw, 
 
 int tvr_act_rows(int32_t fmt, const float* a, int32_t lda, uint16_t* out, int32_t rows, int32_t K,
                  uint32_t* range_flag, void* stream) {
-  if (!a || !out || rows < 0 || K <= 0 || lda < K || (fmt != TVR_GEMM_X2F16 && fmt != TVR_GEMM_BF16))
+  if (!a || !out || rows < 0 || K <= 0 || lda < K ||
+      (fmt != TVR_GEMM_X2F16 && fmt != TVR_GEMM_BF16 && fmt != TVR_ACT_X2F16_IL) ||
+      (fmt == TVR_ACT_X2F16_IL && K % 32 != 0))
     return fail(TVR_ERR_INVALID, "tvr_act_rows: bad argument");
   const size_t n = (size_t)rows * K;
   if (n == 0) return TVR_OK;
   const dim3 grid((unsigned)std::min<size_t>((n + 255) / 256, 8192)), block(256);
   if (fmt == TVR_GEMM_X2F16)
     hipLaunchKernelGGL(act_rows_kernel<ACT_X2F16>, grid, block, 0, (hipStream_t)stream, a, lda, out, rows, K, range_flag);
+  else if (fmt == TVR_ACT_X2F16_IL)
+    hipLaunchKernelGGL(act_rows_kernel<ACT_X2F16I>, grid, block, 0, (hipStream_t)stream, a, lda, out, rows, K, range_flag);
   else
     hipLaunchKernelGGL(act_rows_kernel<ACT_BF16>, grid, block, 0, (hipStream_t)stream, a, lda, out, rows, K, range_flag);
   TVR_HIP(hipGetLastError());
@@ -2798,13 +2878,15 @@ int tvr_gemm_planar(int32_t fmt, const uint16_t* A, int32_t lda, const uint16_t*
                     float w_scale, const float* bias, float* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
                     void* stream) {
   if (!A || !W || !C || M < 0 || N < 0 || K <= 0 || lda < K || !(w_scale > 0.0f) ||
-      (fmt != TVR_GEMM_X2F16 && fmt != TVR_GEMM_BF16) || wps < (size_t)ldw * (N > 0 ? N - 1 : 0) + K)
+      (fmt != TVR_GEMM_X2F16 && fmt != TVR_GEMM_BF16 && fmt != TVR_ACT_X2F16_IL) ||
+      wps < (size_t)ldw * (N > 0 ? N - 1 : 0) + K)
     return fail(TVR_ERR_INVALID, "tvr_gemm_planar: bad argument");
   GemmEpi e{};
   e.bias = bias;
   e.out0 = C;
   e.ld0 = ldc;
-  return launch_gemm(EPI_BIAS, A, lda, fmt == TVR_GEMM_X2F16 ? ACT_X2F16 : ACT_BF16,
+  return launch_gemm(EPI_BIAS, A, lda,
+                     fmt == TVR_GEMM_X2F16 ? ACT_X2F16 : fmt == TVR_ACT_X2F16_IL ? ACT_X2F16I : ACT_BF16,
                      MatW{nullptr, nullptr, W, wps, w_scale}, ldw, M, N, K, e, (hipStream_t)stream);
 }
 

@@ -188,7 +188,7 @@ __device__ __forceinline__ void epi_store(const GemmEpi& ep, size_t orow, int co
       if (mirror) ep.out0m[orow * ep.ld0 + col] = v;
     } else {
       if (ep.raw && orow < (size_t)ep.raw_rows) ep.raw[orow * ep.ld_raw + (col - ep.n_split)] = v;
-      store_act<FMT>(ep.out1h + orow * ep.ld1h + (col - ep.n_split), ep.ps1h, gelu_erf(v), ep.range_flag);
+      store_act<FMT>(ep.out1h + orow * ep.ld1h + act_col<FMT>(col - ep.n_split), act_ps<FMT>(ep.ps1h), gelu_erf(v), ep.range_flag);
     }
   } else {
     ep.out0[orow * ep.ld0 + col] = v + ep.resid[orow * ep.ldr + col];

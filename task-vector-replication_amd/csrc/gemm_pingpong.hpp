@@ -331,7 +331,8 @@ __device__ __forceinline__ void pp_epilogue_lds(const GemmEpi& ep, const f32x4 (
           v[k + 1] = g.y;
         }
         if (!NOSTORE || v[0] == 1.2345e-30f)  // NOSTORE (diagnostic): the LDS pass and math without the stores
-          store_act8<FMT, PP_NT_STORES>(ep.out1h + (size_t)orow[i] * ep.ld1h + (col0 + c8 - ep.n_split), ep.ps1h, v,
+          store_act8<FMT, PP_NT_STORES>(ep.out1h + (size_t)orow[i] * ep.ld1h + act_col<FMT>(col0 + c8 - ep.n_split),
+                                        act_ps<FMT>(ep.ps1h), v,
                                         ep.range_flag, &range_mx);
       }
     } else if (c4 < Nlim) {
@@ -371,7 +372,7 @@ __device__ __forceinline__ void pp_epilogue_lds(const GemmEpi& ep, const f32x4 (
     }
     __syncthreads();
   }
-  if constexpr (EPI == EPI_SPLIT_GELU_ACT && FMT == ACT_X2F16)
+  if constexpr (EPI == EPI_SPLIT_GELU_ACT && act_is_x2(FMT))
     if (range_mx >= X2_FP16_OVERFLOW && ep.range_flag) atomicOr(ep.range_flag, 1u);
 }
 
@@ -398,7 +399,8 @@ struct PpLds {
 // tile (acc * acc_scale, no bias) goes to part as a dense 256 x 256 tile
 // (split-K / stream-K), else the launch's fused epilogue.  (A separate int
 // flag: testing the pointer itself made hipcc spill 26-66 VGPRs.)
-template <int EPI, int FMT, bool VEC, int VAR, bool SL, bool WX = false, bool PFOK = true>
+// AIL: A in the k-tile-interleaved layout (see pp_tile_wt below: 8-row x 128-B pieces, the bf16 form's LDS A image)
+template <int EPI, int FMT, bool VEC, int VAR, bool SL, bool WX = false, bool PFOK = true, bool AIL = false>
 __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda, size_t aps,
                                         const uint16_t* __restrict__ W, int ldw, size_t wps, float acc_scale, int M,
                                         int N, const GemmEpi& ep, int m0, int n0, int kbeg, int nk, float* part, int has_part,
@@ -425,6 +427,11 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
   static_assert(LDS_HALVES * 2 <= 160 * 1024, "LDS budget (P2)");
   static_assert(NPL * KG == 2, "two fragments per 16-row slice per k-tile");
   static_assert(PpLds<FMT>::HALVES * 2 <= 160 * 1024, "LDS budget");
+  static_assert(!AIL || FMT == ACT_X2F16, "the interleaved A layout is an x2f16 form");
+  constexpr int ACPR = AIL ? 8 : CPR;  // 16-B chunks per A row of the LDS image (AIL: both planes in one row)
+  constexpr int ARPP = 64 / ACPR;      // A rows per 1 KB piece
+  constexpr int ABK = ACPR * 8;        // halves per A row of the LDS image
+  constexpr int OFMT = AIL ? (int)ACT_X2F16I : FMT;  // activation-format outputs follow A's layout
   // ONE __shared__ object (a second one can make hipcc drain vmcnt before
   // ds_reads), declared here so every access is a known LDS address (a
   // generic pointer parameter costs VGPRs: 64-bit flat addresses)
@@ -452,18 +459,20 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
     for (int s = 0; s < 2; ++s) {
       // pieces of a one-plane weight region (WX): one per wave (s = 0), plane 0
       const int pi = (WX && R >= 2) ? wave_s : 2 * wave_s + s;
-      const int plane = pi / PPP, x0 = (pi % PPP) * RPP;  // region row of the piece's first row
+      const bool ail = AIL && R < 2;  // 16 pieces of 8 rows x 128 B, no plane index
+      const int plane = ail ? 0 : pi / PPP;
+      const int x0 = ail ? pi * ARPP : (pi % PPP) * RPP;  // region row of the piece's first row
       int trow0;                                          // tile row of it
       if (R < 2)
         trow0 = ((x0 >> 6) << 7) + (x0 & 63) + 64 * R;
       else
         trow0 = ((x0 >> 5) << 6) + (x0 & 31) + 32 * (R - 2);
-      const int row = trow0 + lane / CPR;
-      const int chunk = (lane % CPR) ^ planar_g<CPR>(row);
+      const int row = trow0 + (ail ? lane / ACPR : lane / CPR);
+      const int chunk = ail ? (lane % ACPR) ^ planar_g<ACPR>(row) : (lane % CPR) ^ planar_g<CPR>(row);
       if (R < 2) {
         const int am = min(m0 + row, M - 1);
         src[R][s] = Ab + plane * aps + (size_t)(ep.a_rows ? ep.a_rows[am] : am) * lda + chunk * 8;
-        dst[R][s] = plane * PL + trow0 * BK;
+        dst[R][s] = plane * PL + trow0 * (AIL ? ABK : BK);
       } else {
         src[R][s] = W + plane * wps + (size_t)min(n0 + row, N - 1) * ldw + chunk * 8;
         dst[R][s] = (NPL + plane) * PL + trow0 * BK;
@@ -473,7 +482,8 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
   auto stage = [&](int R, int kt) {
     if (VAR == 1 && kt >= 2) return;
     const bool live = kt < nk;
-    const int koff = live && VAR != 12 ? (kbeg + kt) * BK : 0;  // VAR 12: every k-tile re-reads k-tile 0 (L2-hot)
+    // VAR 12: every k-tile re-reads k-tile 0 (L2-hot); AIL: a k-tile of A is 64 halves
+    const int koff = live && VAR != 12 ? (kbeg + kt) * (AIL && R < 2 ? ABK : BK) : 0;
     const int boff = (P2 ? kt % 3 : kt & 1) * BUF;
 #pragma unroll
     for (int s = 0; s < ((WX && R >= 2) ? 1 : 2); ++s) glds16(src[R][s] + koff, lds + (live ? boff + dst[R][s] : DUMMY));
@@ -486,7 +496,10 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
     const int p = NPL == 2 ? f : 0, g = NPL == 2 ? 0 : f;
     const int ra = wr * 128 + (lane & 15), rb = wc * 64 + (lane & 15);
     const int c = 4 * g + (lane >> 4);
-    aoff[f] = p * PL + ra * BK + ((c ^ planar_g<CPR>(ra)) << 3);
+    if constexpr (AIL)  // plane f is chunks 4 f .. 4 f + 3 of the row: the bf16 form's k-group f
+      aoff[f] = ra * ABK + (((4 * f + (lane >> 4)) ^ planar_g<ACPR>(ra)) << 3);
+    else
+      aoff[f] = p * PL + ra * BK + ((c ^ planar_g<CPR>(ra)) << 3);
     boff[f] = (NPL + p) * PL + rb * BK + ((c ^ planar_g<CPR>(rb)) << 3);
   }
 
@@ -511,14 +524,14 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
     for (int i = 0; i < 4; ++i)
       if (i >= ifirst && (!decltype(part)::value || i0 + i < vi))
 #pragma unroll
-        for (int f = 0; f < 2; ++f) fa[i][f] = *(const frag*)(base + aoff[f] + (i0 + i) * 16 * BK);
+        for (int f = 0; f < 2; ++f) fa[i][f] = *(const frag*)(base + aoff[f] + (i0 + i) * 16 * ABK);
   };
   auto read_fx = [&](const uint16_t* base, auto part) {  // PF: A row tiles 0-1 into fx
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       if (!decltype(part)::value || i < vi)
 #pragma unroll
-        for (int f = 0; f < 2; ++f) fx[i][f] = *(const frag*)(base + aoff[f] + i * 16 * BK);
+        for (int f = 0; f < 2; ++f) fx[i][f] = *(const frag*)(base + aoff[f] + i * 16 * ABK);
   };
   auto read_w = [&](const uint16_t* base, int j0, frag (&fw)[2][2], auto part) {
     if (decltype(part)::value && vi == 0) return;
@@ -817,9 +830,9 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
       pe.out0 = part;
       pe.ld0 = 256;
       pe.out_rows = nullptr;  // partial tiles are stored densely; the reduce applies out_rows
-      pp_epilogue_lds<EPI, FMT, VAR == 8>(pe, acc, L, 0, 0, M - m0, N - n0, wr, wc, lane, t, acc_scale);
+      pp_epilogue_lds<EPI, OFMT, VAR == 8>(pe, acc, L, 0, 0, M - m0, N - n0, wr, wc, lane, t, acc_scale);
     } else {
-      pp_epilogue_lds<EPI, FMT, VAR == 8>(ep, acc, L, m0, n0, M - m0, N - n0, wr, wc, lane, t, acc_scale);
+      pp_epilogue_lds<EPI, OFMT, VAR == 8>(ep, acc, L, m0, n0, M - m0, N - n0, wr, wc, lane, t, acc_scale);
     }
     if ((VAR == 6 || VAR == 8) && ep.stamps && t == 0) {
       unsigned long long* o = ep.stamps + 4 * blockIdx.x;
@@ -843,9 +856,9 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
       GemmEpi pe = ep;
       pe.out0 = part;
       pe.ld0 = 256;
-      gemm_epilogue16t<EPI, FMT, VEC, 8, 4>(pe, acc, M - m0, N - n0, wr * 128, wc * 64, lane);
+      gemm_epilogue16t<EPI, OFMT, VEC, 8, 4>(pe, acc, M - m0, N - n0, wr * 128, wc * 64, lane);
     } else {
-      gemm_epilogue16t<EPI, FMT, VEC, 8, 4>(ep, acc, M, N, m0 + wr * 128, n0 + wc * 64, lane);
+      gemm_epilogue16t<EPI, OFMT, VEC, 8, 4>(ep, acc, M, N, m0 + wr * 128, n0 + wc * 64, lane);
     }
     if (VAR == 6 && ep.stamps && t == 0) {
       unsigned long long* o = ep.stamps + 4 * blockIdx.x;
@@ -884,7 +897,14 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
 #ifndef TVR_WT_SGB
 #define TVR_WT_SGB 1
 #endif
-template <int EPI, int FMT, bool VEC, int VAR, bool SL, bool TWO = false>
+// AIL (x2f16): the A operand in the k-tile-interleaved layout (split.hpp: halves [rows][K / 32][2][32], a row's
+// two planes of one k-tile in one 128-B line).  An A piece is then 8 rows x 128 B (whole lines) instead of 16
+// rows x 64 B (half lines), and the LDS A image is the bf16 form's: 128-B rows, chunks 0-3 plane 0, 4-7 plane
+// 1, planar_g<8> swizzle on the source address.  Same bytes, piece counts, vmcnt counts, fragments, k order.
+// WIL (x2f16, probe only: tools/gemm_split_probe x2ppwxiw): the weight plane row-pair interleaved, halves
+// [N / 2][K / 32][2][32] (ldw = the plane's row stride K, N even) — a W piece's 16 rows x 64 B are then 8 whole
+// lines; the LDS image is unchanged, only the per-lane source address differs.
+template <int EPI, int FMT, bool VEC, int VAR, bool SL, bool TWO = false, bool AIL = false, bool WIL = false>
 __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int lda, size_t aps,
                                            const uint16_t* __restrict__ W, int ldw, float acc_scale, int M, int N,
                                            const GemmEpi& ep, int m0, int n0, int kbeg, int nk, float* part,
@@ -907,6 +927,10 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
   static_assert(!TWO || FMT == ACT_X2F16, "three 64 KB bf16 buffers do not fit the LDS");
   static_assert(NPL * KG == 2, "two A fragments per 16-row tile per k-tile");
   static_assert(!SL || FMT == ACT_X2F16, "the sliced accumulation is an x2f16 form");
+  static_assert(!AIL || FMT == ACT_X2F16, "the interleaved A layout is an x2f16 form");
+  constexpr int ACPR = AIL ? 8 : CPR;  // 16-B chunks per A row of the LDS image (AIL: both planes in one row)
+  constexpr int ARPP = 64 / ACPR;      // A rows per 1 KB piece
+  constexpr int ABK = ACPR * 8;        // halves per A row of the LDS image
   // vmcnt of every phase: the pieces issued after the awaited region (two activation regions of 2 pieces and
   // two weight regions of WP per k-tile; four phases: 4 + 2 WP, the prologue's first wait 4 + 3 WP)
   constexpr int VM = 4 + 2 * WP, VM0 = 4 + 3 * WP;
@@ -914,6 +938,8 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
   constexpr int LDS_HALVES = (NBUF * BUF + 512) > PP_EPI_LDS ? (NBUF * BUF + 512) : PP_EPI_LDS;
   static_assert(LDS_HALVES * 2 <= 160 * 1024, "LDS budget");
   __shared__ __attribute__((aligned(16))) uint16_t lds[LDS_HALVES];
+  // the activation-format outputs (the GELU epilogue's planes) are written in the layout A is read in
+  constexpr int OFMT = AIL ? (int)ACT_X2F16I : FMT;
 
   int t = threadIdx.x;
   asm volatile("" : "+v"(t));
@@ -930,23 +956,30 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int pi = R >= 2 ? WP * wave_s + (WP > 1 ? s : 0) : 2 * wave_s + s;
-      const int plane = pi / PPP, x0 = (pi % PPP) * RPP;  // region row of the piece's first row
+      const bool ail = AIL && R < 2;  // 16 pieces of 8 rows x 128 B, no plane index
+      const int plane = ail ? 0 : pi / PPP;
+      const int x0 = ail ? pi * ARPP : (pi % PPP) * RPP;  // region row of the piece's first row
       const int trow0 = R < 2 ? ((x0 >> 5) << 6) + (x0 & 31) + 32 * R : ((x0 >> 6) << 7) + (x0 & 63) + 64 * (R - 2);
-      const int row = trow0 + lane / CPR;
-      const int chunk = (lane % CPR) ^ planar_g<CPR>(row);
+      const int row = trow0 + (ail ? lane / ACPR : lane / CPR);
+      const int chunk = ail ? (lane % ACPR) ^ planar_g<ACPR>(row) : (lane % CPR) ^ planar_g<CPR>(row);
       if (R < 2) {
         const int am = min(m0 + row, M - 1);
         src[R][s] = Ab + plane * aps + (size_t)(ep.a_rows ? ep.a_rows[am] : am) * lda + chunk * 8;
-        dst[R][s] = plane * PL + trow0 * BK;
+        dst[R][s] = plane * PL + trow0 * (AIL ? ABK : BK);
       } else {
-        src[R][s] = W + (size_t)min(n0 + row, N - 1) * ldw + chunk * 8;
+        const int wn = min(n0 + row, N - 1);
+        if constexpr (WIL)
+          src[R][s] = W + (size_t)(wn >> 1) * (2 * ldw) + (wn & 1) * 32 + chunk * 8;
+        else
+          src[R][s] = W + (size_t)wn * ldw + chunk * 8;
         dst[R][s] = NPL * PL + trow0 * BK;
       }
     }
   }
   auto stage = [&](int R, int kt) {
     const bool live = kt < nk;
-    const int koff = live ? (kbeg + kt) * BK : 0;
+    // (AIL: a k-tile of A is 64 halves; WIL: a k-tile of a W row pair is 64 halves)
+    const int koff = live ? (kbeg + kt) * ((AIL && R < 2) || (WIL && R >= 2) ? 64 : BK) : 0;
     const int boff = (TWO ? kt % 3 : kt & 1) * BUF;
 #pragma unroll
     for (int s = 0; s < (R >= 2 ? WP : 2); ++s) glds16(src[R][s] + koff, lds + (live ? boff + dst[R][s] : DUMMY));
@@ -959,7 +992,10 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
   for (int f = 0; f < 2; ++f) {
     const int p = NPL == 2 ? f : 0, g = NPL == 2 ? 0 : f;
     const int ra = wr * 64 + (lane & 15), c = 4 * g + (lane >> 4);
-    aoff[f] = p * PL + ra * BK + ((c ^ planar_g<CPR>(ra)) << 3);
+    if constexpr (AIL)  // plane f is chunks 4 f .. 4 f + 3 of the row: the bf16 form's k-group f
+      aoff[f] = ra * ABK + (((4 * f + (lane >> 4)) ^ planar_g<ACPR>(ra)) << 3);
+    else
+      aoff[f] = p * PL + ra * BK + ((c ^ planar_g<CPR>(ra)) << 3);
   }
 #pragma unroll
   for (int g = 0; g < KG; ++g) {
@@ -982,7 +1018,7 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
     for (int i = i0; i < i0 + 2; ++i)
       if (!decltype(part)::value || i < vi)
 #pragma unroll
-        for (int f = 0; f < 2; ++f) fa[i][f] = *(const frag*)(base + aoff[f] + i * 16 * BK);
+        for (int f = 0; f < 2; ++f) fa[i][f] = *(const frag*)(base + aoff[f] + i * 16 * ABK);
   };
   auto read_w = [&](const uint16_t* base, int j0, auto part) {
     if (decltype(part)::value && vi == 0) return;
@@ -1163,9 +1199,9 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
       pe.out0 = part;
       pe.ld0 = 256;
       pe.out_rows = nullptr;
-      pp_epilogue_lds<EPI, FMT, VAR == 8, 4, 8>(pe, acc, L, 0, 0, M - m0, N - n0, wr, wc, lane, t, acc_scale);
+      pp_epilogue_lds<EPI, OFMT, VAR == 8, 4, 8>(pe, acc, L, 0, 0, M - m0, N - n0, wr, wc, lane, t, acc_scale);
     } else {
-      pp_epilogue_lds<EPI, FMT, VAR == 8, 4, 8>(ep, acc, L, m0, n0, M - m0, N - n0, wr, wc, lane, t, acc_scale);
+      pp_epilogue_lds<EPI, OFMT, VAR == 8, 4, 8>(ep, acc, L, m0, n0, M - m0, N - n0, wr, wc, lane, t, acc_scale);
     }
     if ((VAR == 6 || VAR == 8) && ep.stamps && t == 0) {
       unsigned long long* o = ep.stamps + 4 * blockIdx.x;
@@ -1189,9 +1225,9 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
       GemmEpi pe = ep;
       pe.out0 = part;
       pe.ld0 = 256;
-      gemm_epilogue16t<EPI, FMT, VEC, 4, 8>(pe, acc, M - m0, N - n0, wr * 64, wc * 128, lane);
+      gemm_epilogue16t<EPI, OFMT, VEC, 4, 8>(pe, acc, M - m0, N - n0, wr * 64, wc * 128, lane);
     } else {
-      gemm_epilogue16t<EPI, FMT, VEC, 4, 8>(ep, acc, M, N, m0 + wr * 64, n0 + wc * 128, lane);
+      gemm_epilogue16t<EPI, OFMT, VEC, 4, 8>(ep, acc, M, N, m0 + wr * 64, n0 + wc * 128, lane);
     }
     if (ep.stamps && t == 0) {
       ep.stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st0;
@@ -1202,7 +1238,7 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
 
 // One tile of a launch: the wide-tile form for one-plane weights (TVR_PP_WX_WIDE 1: four phases, 2: two;
 // VAR 16 / 20 force the four / two-phase wide tile, 17 pp_tile), else pp_tile
-template <int EPI, int FMT, bool VEC, int VAR, bool SL, bool WX, bool SKM>
+template <int EPI, int FMT, bool VEC, int VAR, bool SL, bool WX, bool SKM, bool AIL = false, bool WIL = false>
 __device__ __forceinline__ void pp_tile_any(const uint16_t* __restrict__ A, int lda, size_t aps,
                                             const uint16_t* __restrict__ W, int ldw, size_t wps, float acc_scale,
                                             int M, int N, const GemmEpi& ep, int m0, int n0, int kbeg, int nk,
@@ -1217,13 +1253,15 @@ __device__ __forceinline__ void pp_tile_any(const uint16_t* __restrict__ A, int 
   // both clusters, 16 VGPRs more than the 252 the sliced four-phase form holds — it spilled 38)
   constexpr bool two = FMT == ACT_X2F16 && (VAR == 20 || (VAR != 16 && TVR_PP_WX_WIDE == 2 && !SL));
   constexpr int V = (VAR == 16 || VAR == 17 || VAR == 20) ? 0 : VAR;
+  static_assert(!AIL || FMT == ACT_X2F16, "the interleaved A layout is an x2f16 form");
+  static_assert(!WIL || wide, "the interleaved weight plane: the wide one-plane tile only");
   if constexpr (wide)
-    pp_tile_wt<EPI, FMT, VEC, V, SL, two>(A, lda, aps, W, ldw, acc_scale, M, N, ep, m0, n0, kbeg, nk, part, has_part,
+    pp_tile_wt<EPI, FMT, VEC, V, SL, two, AIL, WIL>(A, lda, aps, W, ldw, acc_scale, M, N, ep, m0, n0, kbeg, nk, part, has_part,
                                           st0, sr0);
   else
     // (the q4 prefetch, TVR_PP_PF, not in the stream-K form or the statistics epilogue: their extra VGPRs
     // there spilled 4 / 8)
-    pp_tile<EPI, FMT, VEC, V, SL, WX, !SKM && EPI != EPI_STATS>(A, lda, aps, W, ldw, wps, acc_scale, M, N, ep, m0, n0,
+    pp_tile<EPI, FMT, VEC, V, SL, WX, !SKM && EPI != EPI_STATS, AIL>(A, lda, aps, W, ldw, wps, acc_scale, M, N, ep, m0, n0,
                                                                 kbeg, nk, part, has_part, st0, sr0);
 }
 
@@ -1238,7 +1276,9 @@ __device__ __forceinline__ void pp_tile_any(const uint16_t* __restrict__ A, int 
 // same instruction stream: timing only), 16 / 17 the one-plane wide / narrow wave tile.  SKM: the stream-K form (sk_blocks
 // blocks; EPI_BIAS partial tiles only).  SL: x2f16 sliced accumulation (above).  WX: x2f16 activations
 // against weights exact in fp16 (one plane staged, two products; pp_tile).
-template <int EPI, int FMT, bool VEC = true, int VAR = 0, bool SKM = false, bool SL = false, bool WX = false>
+// AIL: A in the k-tile-interleaved x2f16 layout (pp_tile_wt; lda = the row stride in halves, aps unused).
+template <int EPI, int FMT, bool VEC = true, int VAR = 0, bool SKM = false, bool SL = false, bool WX = false,
+          bool AIL = false, bool WIL = false>
 __global__ void __launch_bounds__(PP_THREADS, 1)
 gemm_pingpong_kernel(const uint16_t* __restrict__ A, int lda, size_t aps, const uint16_t* __restrict__ W, int ldw,
                      size_t wps, float acc_scale, int M, int N, int K, GemmEpi ep) {
@@ -1273,7 +1313,7 @@ gemm_pingpong_kernel(const uint16_t* __restrict__ A, int lda, size_t aps, const 
       const int nk = (int)min((long long)(nk_all - kbeg), it1 - it);
       int m0, n0;
       pp_tile_coords(ep.tile_base + lt, nbm, nbn, m0, n0, gm);
-      pp_tile_any<EPI, FMT, VEC, VAR, SL, WX, SKM>(A, lda, aps, W, ldw, wps, acc_scale, M, N, ep, m0, n0, kbeg, nk,
+      pp_tile_any<EPI, FMT, VEC, VAR, SL, WX, SKM, AIL, WIL>(A, lda, aps, W, ldw, wps, acc_scale, M, N, ep, m0, n0, kbeg, nk,
                                   ep.out0 + ((size_t)2 * g + seg) * PP_TILE_ELEMS, 1, st0, sr0);
       it += nk;
     };
@@ -1289,7 +1329,7 @@ gemm_pingpong_kernel(const uint16_t* __restrict__ A, int lda, size_t aps, const 
     pp_tile_coords(ep.tile_base + lt, nbm, nbn, m0, n0, gm);
     const int kbeg = (int)((long long)split * nk_all / S);
     const int nk = (int)((long long)(split + 1) * nk_all / S) - kbeg;  // this block's k-tiles
-    pp_tile_any<EPI, FMT, VEC, VAR, SL, WX, SKM>(A, lda, aps, W, ldw, wps, acc_scale, M, N, ep, m0, n0, kbeg, nk,
+    pp_tile_any<EPI, FMT, VEC, VAR, SL, WX, SKM, AIL, WIL>(A, lda, aps, W, ldw, wps, acc_scale, M, N, ep, m0, n0, kbeg, nk,
                                 ep.out0 + ((size_t)split * count + lt) * PP_TILE_ELEMS, S > 1, st0, sr0);
   }
 }

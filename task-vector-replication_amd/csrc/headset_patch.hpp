@@ -22,7 +22,8 @@
 // `slice_bytes` at h * slice_bytes (fp32: 4 d_head, one plane; x2f16: 2 d_head,
 // two planes; bf16: 2 d_head, one plane).  d_head % 16 == 0 (check_config), so
 // every slice is a whole number of 16-byte words, 16-byte aligned.  Zero is
-// all-zero bits in each format.
+// all-zero bits in each format.  il (ACT_X2F16I, split.hpp): the row is k-tile-interleaved — the 16-byte word
+// of plane pl at logical byte offset b of the plane sits at (b / 64) * 128 + b % 64 + 64 pl.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,7 +50,7 @@ template <bool V4>
 __global__ void __launch_bounds__(HEADSET_THREADS)
 headset_patch_kernel(const HeadsetItem* __restrict__ items, const HeadsetPatch* __restrict__ patches,
                      const float* __restrict__ vectors, char* __restrict__ a2, size_t row_bytes, int slice_bytes,
-                     int n_planes, size_t plane_bytes, float* __restrict__ resid, int d) {
+                     int n_planes, size_t plane_bytes, float* __restrict__ resid, int d, int il = 0) {
   const HeadsetItem it = items[blockIdx.x];
   const int r0 = blockIdx.y * HEADSET_ROWS;
   if (r0 >= it.n_rows) return;
@@ -62,8 +63,9 @@ headset_patch_kernel(const HeadsetItem* __restrict__ items, const HeadsetPatch* 
     const int r = x / per_row, y = x - r * per_row;
     const int p = y / per_head, w = y - p * per_head;
     const int pl = w / w16, q = w - pl * w16;
-    char* dst = a2 + (size_t)(it.row0 + r0 + r) * row_bytes + (size_t)pl * plane_bytes +
-                (size_t)ps[p].head * slice_bytes + (size_t)q * 16;
+    const size_t b = (size_t)ps[p].head * slice_bytes + (size_t)q * 16;  // byte offset within the plane
+    char* dst = a2 + (size_t)(it.row0 + r0 + r) * row_bytes +
+                (il ? (b >> 6) * 128 + (b & 63) + (size_t)pl * 64 : (size_t)pl * plane_bytes + b);
     *(uint4*)dst = make_uint4(0u, 0u, 0u, 0u);
   }
 

@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(256) lnpre_kernel(const float* __restrict__ x,
     // trips (14 us per launch at any row count in the C2 sweeps, profiles/r06/c2_trace_r06h.txt)
     constexpr int G = NV < LN_G_F4 ? NV : LN_G_F4;
     [[maybe_unused]] float4 ga[G > 0 ? G : 1], gb[G > 0 ? G : 1];
-    if constexpr (FMT == ACT_X2F16) {
+    if constexpr (act_is_x2(FMT)) {
       if (g1) {
 #pragma unroll
         for (int u = 0; u < G; ++u)
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) lnpre_kernel(const float* __restrict__ x,
     }
     const float scale = sqrtf(wave_sum(ss) / (float)d + eps);
     if (stats && lane == 0) stats[r] = make_float2(mean, scale);
-    if constexpr (FMT == ACT_X2F16) {
+    if constexpr (act_is_x2(FMT)) {
       if (g1) {  // the gamma-scaled row(s): y = x g1 (and y2 = x g2 when y2 is given)
         float mx = 0.f;
 #pragma unroll
@@ -183,12 +183,12 @@ __global__ void __launch_bounds__(256) lnpre_kernel(const float* __restrict__ x,
               const float4 o = make_float4(w.x / scale, w.y / scale, w.z / scale, w.w / scale);
               const float4 a = ga[u];
               const float4 p = make_float4(o.x * a.x, o.y * a.y, o.z * a.z, o.w * a.w);
-              store_ln4<FMT>((uint16_t*)y + (size_t)r * 2 * ldy + 4 * c, ldy, p.x, p.y, p.z, p.w);
+              store_ln4<FMT>((uint16_t*)y + (size_t)r * 2 * ldy + act_col<FMT>(4 * c), act_ps<FMT>(ldy), p.x, p.y, p.z, p.w);
               mx = fmaxf(mx, fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fmaxf(fabsf(p.z), fabsf(p.w))));
               if (y2) {
                 const float4 b = gb[u];
                 const float4 q = make_float4(o.x * b.x, o.y * b.y, o.z * b.z, o.w * b.w);
-                store_ln4<FMT>((uint16_t*)y2 + (size_t)r * 2 * ldy + 4 * c, ldy, q.x, q.y, q.z, q.w);
+                store_ln4<FMT>((uint16_t*)y2 + (size_t)r * 2 * ldy + act_col<FMT>(4 * c), act_ps<FMT>(ldy), q.x, q.y, q.z, q.w);
                 mx = fmaxf(mx, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));
               }
             }
@@ -204,7 +204,7 @@ __global__ void __launch_bounds__(256) lnpre_kernel(const float* __restrict__ x,
         const int c = lane + 64 * u;
         const float4 o = make_float4(v[u].x / scale, v[u].y / scale, v[u].z / scale, v[u].w / scale);
         if constexpr (FMT != ACT_F32) {
-          store_ln4<FMT>((uint16_t*)y + (size_t)r * 2 * ldy + 4 * c, ldy, o.x, o.y, o.z, o.w);
+          store_ln4<FMT>((uint16_t*)y + (size_t)r * 2 * ldy + act_col<FMT>(4 * c), act_ps<FMT>(ldy), o.x, o.y, o.z, o.w);
         } else {
           ((float4*)((float*)y + (size_t)r * ldy))[c] = o;
         }
@@ -232,23 +232,23 @@ __global__ void __launch_bounds__(256) lnpre_kernel(const float* __restrict__ x,
     float4 v = xr[c];
     v.x = (v.x - mean) / scale; v.y = (v.y - mean) / scale;
     v.z = (v.z - mean) / scale; v.w = (v.w - mean) / scale;
-    if constexpr (FMT == ACT_X2F16) {
+    if constexpr (act_is_x2(FMT)) {
       if (g1) {
         const float4 a = ((const float4*)g1)[c];
         const float4 p = make_float4(v.x * a.x, v.y * a.y, v.z * a.z, v.w * a.w);
-        store_ln4<FMT>((uint16_t*)y + (size_t)r * 2 * ldy + 4 * c, ldy, p.x, p.y, p.z, p.w);
+        store_ln4<FMT>((uint16_t*)y + (size_t)r * 2 * ldy + act_col<FMT>(4 * c), act_ps<FMT>(ldy), p.x, p.y, p.z, p.w);
         mx = fmaxf(mx, fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fmaxf(fabsf(p.z), fabsf(p.w))));
         if (y2) {
           const float4 b = ((const float4*)g2)[c];
           const float4 q = make_float4(v.x * b.x, v.y * b.y, v.z * b.z, v.w * b.w);
-          store_ln4<FMT>((uint16_t*)y2 + (size_t)r * 2 * ldy + 4 * c, ldy, q.x, q.y, q.z, q.w);
+          store_ln4<FMT>((uint16_t*)y2 + (size_t)r * 2 * ldy + act_col<FMT>(4 * c), act_ps<FMT>(ldy), q.x, q.y, q.z, q.w);
           mx = fmaxf(mx, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));
         }
         continue;
       }
     }
     if constexpr (FMT != ACT_F32) {
-      store_ln4<FMT>((uint16_t*)y + (size_t)r * 2 * ldy + 4 * c, ldy, v.x, v.y, v.z, v.w);
+      store_ln4<FMT>((uint16_t*)y + (size_t)r * 2 * ldy + act_col<FMT>(4 * c), act_ps<FMT>(ldy), v.x, v.y, v.z, v.w);
     } else {
       ((float4*)((float*)y + (size_t)r * ldy))[c] = v;
     }

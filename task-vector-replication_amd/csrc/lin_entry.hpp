@@ -127,7 +127,8 @@ constexpr int LIN_HALVES = TVR_LIN_HALVES;
 // XCD-aware bijective remap (gemm_pingpong.hpp): the m-blocks that share a
 // head's Wsc tile are consecutive work items, so they run on one XCD together
 // and read that tile from one L2.
-template <int FMT, int NK>
+// OIL: the GELU planes (out1h: a2's columns after z) are written in the k-tile-interleaved layout (ACT_X2F16I)
+template <int FMT, int NK, bool OIL = false>
 __global__ void
 #if TVR_LIN_WAVES > 0
 __launch_bounds__(LIN_THREADS, TVR_LIN_WAVES)
@@ -288,7 +289,9 @@ lin_entry_kernel(const LinMB* __restrict__ mbs, int n_mb, const LinRow* __restri
         *(f32x4*)(qkv + (size_t)q[i].x * n3 + n0) = y;
       } else {
         const f32x2 g01 = gelu_erf2(f32x2{y[0], y[1]}), g23 = gelu_erf2(f32x2{y[2], y[3]});
-        store_act4<FMT>(out1h + (size_t)q[i].x * ld1h + (n0 - n3), ps1h, g01.x, g01.y, g23.x, g23.y, range_flag);
+        constexpr int OF = OIL ? (int)ACT_X2F16I : FMT;
+        store_act4<OF>(out1h + (size_t)q[i].x * ld1h + act_col<OF>(n0 - n3), act_ps<OF>(ps1h), g01.x, g01.y, g23.x,
+                       g23.y, range_flag);
       }
     }
   }

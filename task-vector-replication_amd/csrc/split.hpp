@@ -47,7 +47,33 @@ __device__ __forceinline__ void wave_argmax(float& bv, int& bi) {
 // ACT_F16: one fp16 plane, read from plane 1 of a TVR_GEMM_BF16 LayerNorm
 // output (store_ln4): the operand format of that mode's attention-score
 // projections (Q, K columns of W1), see engine.hip launch_w1.
-enum ActFmt { ACT_F32 = 0, ACT_X2F16 = 1, ACT_BF16 = 2, ACT_F16 = 3 };
+//
+// ACT_X2F16I: ACT_X2F16's values in the k-tile-interleaved layout, halves [R][K / 32][2][32] (K % 32 == 0): per
+// row and 32-column group 64 B of plane 0, then 64 B of plane 1 — one 128-B line, which the one-plane GEMM
+// (gemm_pingpong.hpp pp_tile_wt, AIL) stages as whole lines.  Same values, same bytes per row, different
+// addresses: column c of plane p sits at act_col(c) + p * act_ps(.).  The exact-fp16 sweeps' GEMM inputs (xn,
+// xn2, a2, xf) use it unless TVR_ACT_LAYOUT=planar; producers address through act_col / act_ps, whose 4- and
+// 8-element groups (column % 4 / % 8 == 0) never straddle a 32-column group.
+enum ActFmt { ACT_F32 = 0, ACT_X2F16 = 1, ACT_BF16 = 2, ACT_F16 = 3, ACT_X2F16I = 4 };
+
+constexpr bool act_is_x2(int fmt) { return fmt == ACT_X2F16 || fmt == ACT_X2F16I; }
+// offset (halves, within the row) of logical column c's plane-0 element
+template <int FMT>
+__host__ __device__ __forceinline__ int act_col(int c) {
+  if constexpr (FMT == ACT_X2F16I)
+    return ((c >> 5) << 6) + (c & 31);
+  else
+    return c;
+}
+// plane stride (halves) of a buffer whose planar plane stride would be `plane`
+template <int FMT>
+__host__ __device__ __forceinline__ int act_ps(int plane) {
+  if constexpr (FMT == ACT_X2F16I)
+    return 32;
+  else
+    return plane;
+}
+inline int act_col_rt(int fmt, int c) { return fmt == ACT_X2F16I ? act_col<ACT_X2F16I>(c) : c; }
 
 #ifndef TVR_X2_ASCALE
 #define TVR_X2_ASCALE 16.0f
@@ -78,7 +104,7 @@ __device__ __forceinline__ uint16_t bf16_bits(float a) { return __builtin_bit_ca
 // one element in activation format FMT (ACT_X2F16 / ACT_BF16)
 template <int FMT>
 __device__ __forceinline__ void store_act(uint16_t* p, int plane, float a, unsigned* flag) {
-  if constexpr (FMT == ACT_X2F16)
+  if constexpr (act_is_x2(FMT))
     store_split(p, plane, a, flag);
   else
     p[0] = bf16_bits(a);
@@ -104,7 +130,7 @@ __device__ __forceinline__ void split_f16x2(float a, float b, unsigned& h0, unsi
 template <int FMT>
 __device__ __forceinline__ void store_act4(uint16_t* p, int plane, float a, float b, float c, float d,
                                            unsigned* flag) {
-  if constexpr (FMT == ACT_X2F16) {
+  if constexpr (act_is_x2(FMT)) {
     unsigned l0, l1, h0, h1;
     float m = 0.f;
     split_f16x2(a, b, l0, h0, m);
@@ -146,7 +172,7 @@ __device__ __forceinline__ void store_act8(uint16_t* p, int plane, const float (
     else
       *(u32x4*)q = x;
   };
-  if constexpr (FMT == ACT_X2F16) {
+  if constexpr (act_is_x2(FMT)) {
     unsigned lo[4], hi[4];
     float m = 0.f;
 #pragma unroll
@@ -165,14 +191,14 @@ __device__ __forceinline__ void store_act8(uint16_t* p, int plane, const float (
   }
 }
 
-// fp32 rows a [rows][lda] -> activation format FMT with K logical columns
+// fp32 rows a [rows][lda] -> activation format FMT with K logical columns (row stride 2 K halves)
 template <int FMT>
 __global__ void act_rows_kernel(const float* __restrict__ a, int lda, uint16_t* __restrict__ out, int rows, int K,
                                 unsigned* __restrict__ flag) {
   const size_t n = (size_t)rows * K;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const size_t r = i / K, c = i % K;
-    store_act<FMT>(out + r * 2 * K + c, K, a[r * lda + c], flag);
+    store_act<FMT>(out + r * 2 * K + act_col<FMT>((int)c), act_ps<FMT>(K), a[r * lda + c], flag);
   }
 }
 

@@ -9,6 +9,9 @@
 //     x2pt = K-loop anatomy (cycles in vmcnt drain / barrier, waves 0 and 7)
 //     bf16 = the planar kernel on one bf16 plane (TVR_GEMM_BF16; its error is the bf16 rounding)
 //     x2pp / bf16pp = the phase-split two-group schedule (gemm_pingpong.hpp); bf16 paths last
+//     x2ppwxi / x2pp6wxi = x2ppwx / x2pp6wx (one-plane wide two-phase kernel) with A k-tile-interleaved:
+//       8-row x 128-B staging pieces instead of 16-row x 64-B (a path may be named more than once: A B A B ...)
+//     x2ppwxiw = x2ppwxi with the weight plane row-pair interleaved as well (W pieces of 8 whole lines)
 // A is drawn N(0,1) (a LayerNorm output) or GELU(3 N(0,1)) (the MLP-out input:
 // many tiny values, which exercises the fp16 residual plane's range).
 #include <hip/hip_runtime.h>
@@ -42,6 +45,30 @@ __global__ void round_f16_kernel(float* p, size_t n) {  // weights exact in fp16
     p[i] = (float)(_Float16)p[i];
 }
 
+// A [M][K] fp32 -> the k-tile-interleaved x2f16 layout, halves [M][K / 32][2][32] (a row's two planes of one
+// k-tile in one 128-B line): the wxi paths' A operand
+__global__ void split_act_f16_il_kernel(const float* __restrict__ a, uint16_t* __restrict__ out, size_t M, int K) {
+  const size_t n = M * K;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / K;
+    const int c = (int)(i % K);
+    const SplitF16 h = split_f16(a[i]);
+    uint16_t* o = out + r * 2 * K + (size_t)(c >> 5) * 64 + (c & 31);
+    o[0] = h.h0;
+    o[32] = h.h1;
+  }
+}
+
+// one fp16 plane W [N][K] -> row-pair interleaved [N / 2][K / 32][2][32] (N even, K % 32 == 0): the wxiw path
+__global__ void weight_plane_il_kernel(const uint16_t* __restrict__ w, uint16_t* __restrict__ out, size_t N, int K) {
+  const size_t n = N * K;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / K;
+    const int c = (int)(i % K);
+    out[(r >> 1) * 2 * K + (size_t)(c >> 5) * 64 + (r & 1) * 32 + (c & 31)] = w[i];
+  }
+}
+
 __global__ void ref64(const float* A, const float* W, const int* rows, int nr, int N, int K, double* out, double* mag) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= nr * N) return;
@@ -62,7 +89,7 @@ int main(int argc, char** argv) {
   std::vector<Shape> shapes = {{"qkv_mlpin", 90000, 17920, 2560, 0}, {"o_mlpout", 90000, 2560, 12800, 1}};
   for (auto& s : shapes) {
     float *A, *W, *C;
-    uint16_t *W3, *W2, *A2;
+    uint16_t *W3, *W2, *A2, *A2I = nullptr, *W2I = nullptr;
     unsigned *flag, *wmax_bits;
     unsigned long long* stamps;
     const int maxgrid = gemm_grid<TileSmall>(s.M, s.N);
@@ -92,6 +119,14 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(split_planes_f16_kernel, dim3(8192), dim3(256), 0, 0, W, wscale, W2, (size_t)s.N * s.K);
     const float acc_scale = 1.0f / (wscale * X2_ASCALE);
     hipLaunchKernelGGL(split_act_f16_kernel, dim3(8192), dim3(256), 0, 0, A, A2, (size_t)s.M * s.K);
+    bool ail = false;  // any interleaved-A path: a second copy of A in that layout
+    for (const auto& p : paths) ail = ail || p == "x2ppwxi" || p == "x2pp6wxi" || p == "x2ppwxiw";
+    if (ail) {
+      hipMalloc(&A2I, sizeof(uint16_t) * 2 * (size_t)s.M * s.K);
+      hipLaunchKernelGGL(split_act_f16_il_kernel, dim3(8192), dim3(256), 0, 0, A, A2I, (size_t)s.M, s.K);
+      hipMalloc(&W2I, sizeof(uint16_t) * (size_t)s.N * s.K);
+      hipLaunchKernelGGL(weight_plane_il_kernel, dim3(8192), dim3(256), 0, 0, W2, W2I, (size_t)s.N, s.K);
+    }
 
     // accuracy rows
     const int nr = 64;
@@ -218,6 +253,17 @@ int main(int argc, char** argv) {
           GemmEpi eg = ee;
           hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_BF16, true, 6>), dim3(grid), dim3(PP_THREADS), 0, 0,
                              A2, 2 * s.K, (size_t)s.K, W2, s.K, (size_t)s.N * s.K, 1.0f, s.M, s.N, s.K, eg);
+        } else if (path == "x2ppwxi" || path == "x2pp6wxi") {  // interleaved A (row stride 2 K halves), timed / anatomy
+          grid = gemm_pingpong_grid(s.M, s.N);
+          auto ki = path == "x2ppwxi" ? gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, false, true, true>
+                                      : gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 6, false, false, true, true>;
+          hipLaunchKernelGGL(ki, dim3(grid), dim3(PP_THREADS), 0, 0,
+                             A2I, 2 * s.K, (size_t)0, W2, s.K, (size_t)s.N * s.K, acc_scale, s.M, s.N, s.K, ee);
+        } else if (path == "x2ppwxiw") {  // interleaved A and row-pair interleaved W
+          grid = gemm_pingpong_grid(s.M, s.N);
+          hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, false, true, true, true>),
+                             dim3(grid), dim3(PP_THREADS), 0, 0, A2I, 2 * s.K, (size_t)0, W2I, s.K, (size_t)s.N * s.K,
+                             acc_scale, s.M, s.N, s.K, ee);
         } else if (path == "x2pp6wx" || path == "x2pp6gwx") {  // anatomy of the one-plane (wide) kernel
           grid = gemm_pingpong_grid(s.M, s.N);
           GemmEpi eg = ee;
@@ -274,7 +320,7 @@ int main(int argc, char** argv) {
         }
       };
       if (path == "x2pp6" || path == "x2pp6g" || path == "x2pp8" || path == "x2pp6wx" || path == "x2pp6gwx" ||
-          path == "bf16pp6") {
+          path == "x2pp6wxi" || path == "bf16pp6") {
         // block anatomy: medians over blocks (cycles)
         for (int i = 0; i < 5; ++i) run(false);
         run(true);
@@ -355,7 +401,7 @@ int main(int argc, char** argv) {
              mhz, emax, sqrt(erms / ((double)nr * s.N)), hflag);
       fflush(stdout);
     }
-    hipFree(A); hipFree(A2); hipFree(W); hipFree(W3); hipFree(W2); hipFree(C); hipFree(flag); hipFree(wmax_bits);
+    hipFree(A); hipFree(A2); hipFree(A2I); hipFree(W2I); hipFree(W); hipFree(W3); hipFree(W2); hipFree(C); hipFree(flag); hipFree(wmax_bits);
     hipFree(stamps); hipFree(drows); hipFree(ref); hipFree(mag);
   }
   return 0;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel means of a rocprofv3 --pmc counter_collection.csv (tools/pmc_probe.sh): wave-cycle split
 (quad-cycles, MI355X_MICROARCH.md 'rocprofv3 PMC slots'), MFMA busy per SIMD-cycle, the clock from
-GRBM_GUI_ACTIVE / 8 XCDs over the dispatch time."""
+GRBM_GUI_ACTIVE / 8 XCDs over the dispatch time, TA busy (TA_BUSY_avr over the same cycles)."""
 import csv
 import glob
 import sys
@@ -28,5 +28,6 @@ for k, c in agg.items():
            "active_inst": c["SQ_ACTIVE_INST_ANY"] / wc, "wait_inst_lds": c["SQ_WAIT_INST_LDS"] / wc,
            "lds_bank_conflict_per_lds_inst": c["SQ_LDS_BANK_CONFLICT"] / max(1.0, c["SQ_INSTS_LDS"]),
            "mfma_busy": c["SQ_VALU_MFMA_BUSY_CYCLES"] / max(1.0, gui * 1024),
+           "ta_busy": c["TA_BUSY_avr"] / max(1.0, gui),  # busy cycles averaged over the TA units / shader cycles
            "clock_ghz": gui / ns if ns else None}
     print(k[-90:], {a: (round(b, 4) if isinstance(b, float) else b) for a, b in out.items()})

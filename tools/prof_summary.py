@@ -126,7 +126,8 @@ def mfma_util(rows, fam_only=None):
     over every SIMD) / (SIMDs x shader cycles), shader cycles = GRBM_GUI_ACTIVE / 8
     (rocprofv3 sums it over the 8 XCDs; MI355X_MICROARCH.md DVFS note); the
     effective clock is those cycles over the dispatch's wall time.  SQ wave
-    states (quad-cycles) as fractions of SQ_WAVE_CYCLES."""
+    states (quad-cycles) as fractions of SQ_WAVE_CYCLES.  TA_BUSY_avr (busy cycles averaged over the
+    texture-address units, when the pass collected it) over the same shader cycles: ta_busy."""
     by = {}
     for r in rows:
         gv = gemm_variant(r["Kernel_Name"])
@@ -137,7 +138,7 @@ def mfma_util(rows, fam_only=None):
     per = {}
     for (_, (fam, v)), d in by.items():
         p = per.setdefault(VARIANTS[v], {"launches": 0, "busy": 0.0, "grbm": 0.0, "ns": 0,
-                                         "wave": 0.0, "wait": 0.0, "wait_inst": 0.0, "active": 0.0})
+                                         "wave": 0.0, "wait": 0.0, "wait_inst": 0.0, "active": 0.0, "ta": 0.0})
         p["launches"] += 1
         p["busy"] += d.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0)
         p["grbm"] += d.get("GRBM_GUI_ACTIVE", 0.0)
@@ -146,6 +147,7 @@ def mfma_util(rows, fam_only=None):
         p["wait"] += d.get("SQ_WAIT_ANY", 0.0)
         p["wait_inst"] += d.get("SQ_WAIT_INST_ANY", 0.0)
         p["active"] += d.get("SQ_ACTIVE_INST_ANY", 0.0)
+        p["ta"] += d.get("TA_BUSY_avr", 0.0)
     def fmt(p):
         cyc = p["grbm"] / 8
         out = {"launches": p["launches"], "mfma_util": round(p["busy"] / (SIMDS * cyc), 4) if cyc else None,
@@ -154,9 +156,11 @@ def mfma_util(rows, fam_only=None):
             out.update({"wave_wait_any": round(p["wait"] / p["wave"], 3),
                         "wave_wait_inst": round(p["wait_inst"] / p["wave"], 3),
                         "wave_active_inst": round(p["active"] / p["wave"], 3)})
+        if p["ta"] and cyc:
+            out["ta_busy"] = round(p["ta"] / cyc, 4)
         return out
     tot = {k: sum(p[k] for p in per.values()) for k in ("launches", "busy", "grbm", "ns", "wave", "wait",
-                                                          "wait_inst", "active")}
+                                                          "wait_inst", "active", "ta")}
     res = {"basis": "SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8); clock = "
                     "GRBM_GUI_ACTIVE / 8 / dispatch time", "all": fmt(tot)}
     res["variants"] = {k: fmt(p) for k, p in per.items()}
