@@ -74,7 +74,25 @@ enum tvr_site_kind {
    *   the last-token intervention of the function-vector paper).
    * The site's own layer / head / vec fields are ignored. */
   TVR_SITE_REPLACE_HEADSET_ALLPOS = 4,
-  TVR_SITE_REPLACE_HEADSET_LASTPOS = 5
+  TVR_SITE_REPLACE_HEADSET_LASTPOS = 5,
+  /* blocks.{layer}.hook_resid_pre[0, pos, :] = vectors[vec], then
+   * forward(start_at_layer=layer): a caller's vector written into the residual
+   * stream (Hendel et al.'s task-vector patch: theta(layer) at the last position
+   * of a zero-shot prompt).  Fields seq, layer, pos, vec, target.  Planned as
+   * TVR_SITE_SET_RESID_PRE_POS: the site enters at `layer` and computes rows
+   * [pos, T), so a last-position site is one row on the single-query attention.
+   * `vectors` holds TransformerLens' (centred) residual values, e.g. rows of
+   * tvr_trace_capture_resid or tvr_trace_read.  With exact-fp16 weights bound
+   * (tvr_model_set_exact16) the clean rows carry one constant per row and the
+   * vector is written as it is: the patched row's constant is then zero, which
+   * every LayerNorm and the centred export tolerate (results equal the
+   * processed-weight path's to fp32 rounding).  The entry kernel reads `vectors`
+   * element-wise for this kind: float (4 B) alignment suffices.  Accepted by
+   * tvr_patch_sweep and tvr_patch_sweep_sets (there it owns an empty patch
+   * range); on a filled trace or a deferred clean forward, every GEMM path.
+   * TVR_ERR_INVALID for layer, pos or vec out of range or null vectors.
+   * (Backward-compatible addition: ABI 11.) */
+  TVR_SITE_SET_RESID_PRE_VEC = 6
 };
 
 typedef struct tvr_config {
@@ -110,10 +128,10 @@ typedef struct tvr_site {
   int32_t kind;     /* enum tvr_site_kind */
   int32_t layer;    /* hook layer */
   int32_t head;     /* REPLACE_HEAD_ALLPOS */
-  int32_t pos;      /* SET_RESID_PRE_POS: patched position in `seq` (>= 0) */
+  int32_t pos;      /* SET_RESID_PRE_POS / _VEC: patched position in `seq` (>= 0) */
   int32_t src_seq;  /* SET_RESID_PRE_POS: sequence supplying the row */
   int32_t src_pos;  /* SET_RESID_PRE_POS: position supplying the row */
-  int32_t vec;      /* row of `vectors` (REPLACE / ADD) */
+  int32_t vec;      /* row of `vectors` (REPLACE / ADD / SET_RESID_PRE_VEC) */
   int32_t target;   /* token whose probability is reported, -1: none */
 } tvr_site;
 
@@ -212,6 +230,27 @@ enum tvr_trace_hook { TVR_TRACE_RESID_PRE = 0, TVR_TRACE_Z = 1 };
 int tvr_trace_read(const tvr_trace* trace, int32_t what, int32_t layer, float* dst,
                    void* stream);
 int32_t tvr_trace_num_tokens(const tvr_trace* trace);
+/* Grouped residual capture (Hendel et al.'s task-vector extraction):
+ * out[g][l][:] += sum over sequences s with group[s] == g of
+ * blocks.{l}.hook_resid_pre[row(s)]  (l == n_layers: the final residual),
+ * row(s) = seq_off[s] + (pos ? pos[s] : seq_len[s] - 1), every l in [0, n_layers]
+ * in one launch sequence.  Values are TransformerLens' (centred): on a trace
+ * filled on the exact-fp16 path the per-row constant is removed, as
+ * tvr_trace_read does.  pos host [n_seq] or NULL (last position); group host
+ * [n_seq] in [0, n_groups) or NULL (one group); out device
+ * [n_groups][n_layers + 1][d] fp32, float alignment (4 B) suffices: it is read
+ * and written element-wise.  A group without sequences leaves its rows of out
+ * untouched.  Runs a pending deferred clean forward first.  Sums run in a fixed
+ * order that depends only on the group's sequence list (chunks of 16
+ * sequences in sequence order, then the chunks in order), never on the launch
+ * geometry: results are bitwise reproducible for a given trace.  group =
+ * identity gives per-prompt vectors, n_groups = n_tasks many tasks from one
+ * forward.  All arguments are validated before any device call:
+ * TVR_ERR_INVALID for a null trace or out, an empty trace, a pos outside
+ * [0, seq_len), a group outside [0, n_groups), n_groups <= 0.
+ * (Backward-compatible addition: ABI 11.) */
+int tvr_trace_capture_resid(tvr_trace* trace, const int32_t* pos, const int32_t* group,
+                            int32_t n_groups, float* out, void* stream);
 
 /* Batched clean forward of n_seq prompts (ragged lengths, packed tokens).
  * Replaces the per-prompt model.forward / run_with_cache calls
@@ -269,8 +308,8 @@ int tvr_patch_sweep(tvr_model* model, tvr_trace* trace,
                     const float* vectors, int32_t n_vectors, float* out_prob,
                     int32_t* out_topk, int32_t topk, float* out_logits,
                     void* stream);
-/* (tvr_patch_sweep takes kinds 0-3; it rejects the head-set kinds 4 and 5 with
- * TVR_ERR_INVALID and a message naming tvr_patch_sweep_sets.) */
+/* (tvr_patch_sweep takes kinds 0-3 and 6; it rejects the head-set kinds 4 and 5
+ * with TVR_ERR_INVALID and a message naming tvr_patch_sweep_sets.) */
 
 /* tvr_patch_sweep with head-set sites: one patched forward replaces the
  * hook_result of a SET of (layer, head) pairs at once — the joint mean-ablation
@@ -278,7 +317,7 @@ int tvr_patch_sweep(tvr_model* model, tvr_trace* trace,
  * writes as one run_with_hooks call with one scratch2.py:188 hook per member.
  *   set_off  host [n_sites + 1], non-decreasing, set_off[0] >= 0: a site of
  *            kind TVR_SITE_REPLACE_HEADSET_ALLPOS / _LASTPOS owns
- *            patches[set_off[i] .. set_off[i+1]); a site of kinds 0-3 must own
+ *            patches[set_off[i] .. set_off[i+1]); a site of kinds 0-3 or 6 must own
  *            an empty range and behaves exactly as in tvr_patch_sweep (mixed
  *            launches are fine).  An empty set equals TVR_SITE_NONE.
  *   patches  host [set_off[n_sites]] (the caller guarantees that length; may be
@@ -297,7 +336,8 @@ int tvr_patch_sweep(tvr_model* model, tvr_trace* trace,
  *            TVR_SITE_REPLACE_HEAD_ALLPOS read `vectors` with 16-byte loads:
  *            a launch that holds such a site with a base that is not 16-byte
  *            aligned returns TVR_ERR_INVALID here (tvr_patch_sweep does not
- *            check: pass it a 16-byte aligned base).
+ *            check: pass it a 16-byte aligned base).  TVR_SITE_SET_RESID_PRE_VEC
+ *            reads it element-wise: float alignment suffices in both sweeps.
  * A set site enters the staircase at its lowest patched layer and computes
  * every layer from there (ALLPOS: all T rows; LASTPOS: the last row, against
  * the clean K/V).  Works on a filled trace and on a deferred clean forward, on
@@ -392,7 +432,8 @@ enum tvr_hbm_kind {
                            * clean rows in, patched rows out, z rows + W_O slice per head; and the head-set
                            * patches of tvr_patch_sweep_sets, one launch per patched layer: z slices zeroed +
                            * residual rows read and written + vectors read */
-  TVR_HBM_CAPTURE = 1,    /* extraction: sum of hook_z at every prompt's last row -> [d] per layer */
+  TVR_HBM_CAPTURE = 1,    /* extraction: sum of hook_z at every prompt's last row -> [d] per layer; and
+                           * tvr_trace_capture_resid: rows read x (L + 1) x d x 4 + out read and written */
   TVR_HBM_LNPRE = 2,      /* LayerNormPre rows -> GEMM input format */
   TVR_HBM_ATTENTION = 3,  /* attention: fp32 Q/K/V rows in, z out (activation format [+ fp32 hook_z]) */
   TVR_HBM_ROW_STATS = 4,  /* softmax target probability / top-k over one logit row per site */

@@ -13,7 +13,8 @@ from .config import PythiaConfig, get_config
 from .model import Model, Trace, make_sites
 from .results import load_results, save_results
 from .experiments import (apply_layered_vectors_to_zero_shot, apply_layered_vectors_to_zero_shot_by_probability,
-                          assemble_end_list_tasks, assemble_task_vector, calculate_average_causal_indirect_effect,
+                          apply_task_vectors_to_zero_shot, apply_task_vectors_to_zero_shot_by_probability,
+                          extract_task_vectors, assemble_end_list_tasks, assemble_task_vector, calculate_average_causal_indirect_effect,
                           check_accuracy_of_added_task_vector, check_accuracy_of_task_vector,
                           gather_head_activations_to_layers, generate_mean_activation, generate_shuffled_prompt,
                           generate_shuffled_prompts, head_ablation_curve, joint_head_patch_effect,

@@ -38,6 +38,7 @@ SITE_ADD_ATTN_OUT_LASTPOS = 2
 SITE_SET_RESID_PRE_POS = 3
 SITE_REPLACE_HEADSET_ALLPOS = 4  # tvr_patch_sweep_sets only
 SITE_REPLACE_HEADSET_LASTPOS = 5
+SITE_SET_RESID_PRE_VEC = 6  # hook_resid_pre[layer][0, pos] = vectors[vec] (either sweep)
 
 c_f32p = ctypes.c_void_p
 c_i32p = ctypes.c_void_p
@@ -101,6 +102,8 @@ SIGNATURES = {
     "tvr_trace_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_f32p,
                                       ctypes.c_void_p]),
     "tvr_trace_num_tokens": (ctypes.c_int32, [ctypes.c_void_p]),
+    "tvr_trace_capture_resid": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, ctypes.c_int32, c_f32p,
+                                               ctypes.c_void_p]),
     "tvr_forward_clean": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32p, c_i32p, ctypes.c_int32,
                                          c_i32p, c_f32p, c_i32p, ctypes.c_int32, c_f32p, c_f32p,
                                          ctypes.c_void_p]),
@@ -154,6 +157,8 @@ OPS_PATH = LIB_PATH.parent / OPS_NAME
 OPS = ("forward_clean", "patch_sweep", "project_heads", "forward_logits")
 # the joint head-set sweep (tvr_patch_sweep_sets), registered by the same extension
 SET_OPS = ("patch_sweep_sets",)
+# the grouped residual capture (tvr_trace_capture_resid), registered by the same extension
+RESID_OPS = ("capture_resid",)
 
 _LIB = None
 _OPS_LOADED = False

@@ -1883,6 +1883,84 @@ int tvr_trace_read(const tvr_trace* t, int32_t what, int32_t layer, float* dst, 
 
 int32_t tvr_trace_num_tokens(const tvr_trace* t) { return t ? t->n_tokens : 0; }
 
+int tvr_trace_capture_resid(tvr_trace* t, const int32_t* pos, const int32_t* group, int32_t n_groups, float* out,
+                            void* stream) {
+  if (!t || !out) return fail(TVR_ERR_INVALID, "tvr_trace_capture_resid: null argument");
+  if (t->n_seq <= 0) return fail(TVR_ERR_INVALID, "tvr_trace_capture_resid: trace is empty: run tvr_forward_clean first");
+  if (n_groups <= 0) return fail(TVR_ERR_INVALID, "tvr_trace_capture_resid: n_groups must be positive");
+  tvr_model* m = t->model;
+  const int L = m->cfg.n_layers, d = m->cfg.d_model, n_seq = t->n_seq;
+  const size_t lds = (size_t)d * sizeof(float);  // one row of sums per wave
+  if (d % 4 != 0 || lds > 64 * 1024)
+    return fail(TVR_ERR_UNSUPPORTED, "tvr_trace_capture_resid: d_model must be a multiple of 4, at most 16384");
+  for (int s = 0; s < n_seq; ++s) {
+    if (pos && (pos[s] < 0 || pos[s] >= t->seq_len[s]))
+      return fail(TVR_ERR_INVALID, "tvr_trace_capture_resid: pos of sequence " + std::to_string(s) + " out of range");
+    if (group && (group[s] < 0 || group[s] >= n_groups))
+      return fail(TVR_ERR_INVALID, "tvr_trace_capture_resid: group of sequence " + std::to_string(s) + " out of range");
+  }
+  // the sequences sorted by group (stable: sequence order within a group), each group cut into chunks of
+  // RESID_CAP_CHUNK rows; a group of several chunks gets consecutive partial slots and one finish item
+  std::vector<int> order(n_seq);
+  for (int s = 0; s < n_seq; ++s) order[s] = s;
+  if (group) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return group[a] < group[b]; });
+  std::vector<int32_t> rows(n_seq);
+  for (int k = 0; k < n_seq; ++k) {
+    const int s = order[k];
+    rows[k] = t->seq_off[s] + (pos ? pos[s] : t->seq_len[s] - 1);
+  }
+  std::vector<ResidCapChunk> chunks;
+  std::vector<ResidCapFinish> fins;
+  int n_slots = 0;
+  for (int k0 = 0; k0 < n_seq;) {
+    const int g = group ? group[order[k0]] : 0;
+    int k1 = k0;
+    while (k1 < n_seq && (group ? group[order[k1]] : 0) == g) ++k1;
+    const int nch = (k1 - k0 + RESID_CAP_CHUNK - 1) / RESID_CAP_CHUNK;
+    if (nch > 1) fins.push_back(ResidCapFinish{g, n_slots, nch, 0});
+    for (int j = 0; j < nch; ++j) {
+      const int r0 = k0 + j * RESID_CAP_CHUNK;
+      chunks.push_back(ResidCapChunk{r0, std::min(RESID_CAP_CHUNK, k1 - r0), g, nch > 1 ? n_slots++ : -1});
+    }
+    k0 = k1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  TVR_TRY(flush_pending(t, stream));  // a deferred clean forward runs now (it uses the workspace: carve after it)
+  Carve cv;
+  const size_t o_rows = cv.take<int32_t>(rows.size());
+  const size_t o_chunks = cv.take<ResidCapChunk>(chunks.size());
+  const size_t o_fins = cv.take<ResidCapFinish>(fins.size());
+  const size_t o_part = cv.take<float>((size_t)(L + 1) * n_slots * d);
+  TVR_TRY(ensure_workspace(m, cv.off, st));
+  char* base = m->ws;
+  UploadBatch ub;
+  ub.add(o_rows, rows);
+  ub.add(o_chunks, chunks);
+  if (!fins.empty()) ub.add(o_fins, fins);
+  TVR_TRY(flush_uploads(m, st, base, ub));
+  const size_t lstride = (size_t)t->max_tokens * d;
+  float* part = (float*)(base + o_part);
+  ProfSpan ps(m, st);
+  const dim3 g1((unsigned)chunks.size(), L + 1);
+  if (t->uncentred)
+    hipLaunchKernelGGL(resid_capture_partial_kernel<true>, g1, dim3(64), lds, st, t->resid, lstride,
+                       (const int32_t*)(base + o_rows), (const ResidCapChunk*)(base + o_chunks), n_slots, part, out,
+                       L + 1, d);
+  else
+    hipLaunchKernelGGL(resid_capture_partial_kernel<false>, g1, dim3(64), lds, st, t->resid, lstride,
+                       (const int32_t*)(base + o_rows), (const ResidCapChunk*)(base + o_chunks), n_slots, part, out,
+                       L + 1, d);
+  TVR_HIP(hipGetLastError());
+  if (!fins.empty()) {
+    hipLaunchKernelGGL(resid_capture_finish_kernel, dim3((unsigned)fins.size(), (d + 255) / 256, L + 1), dim3(256), 0,
+                       st, part, n_slots, (const ResidCapFinish*)(base + o_fins), out, L + 1, d);
+    TVR_HIP(hipGetLastError());
+  }
+  // rows read x (L + 1) x d x 4, plus out read and written
+  ps.done(TVR_HBM_CAPTURE, ((double)n_seq + 2.0 * n_groups) * (L + 1) * d * 4.0);
+  return TVR_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -2139,7 +2217,7 @@ int tvr_forward_logits(tvr_model* m, const int32_t* tokens, const float* resid_i
 
 
 // The body of tvr_patch_sweep and tvr_patch_sweep_sets.  set_off == nullptr: the plain sweep (kinds 0-3
-// only); else sites of kinds 4 / 5 own patches[set_off[i], set_off[i + 1]) and the other kinds own nothing.
+// and 6 only); else sites of kinds 4 / 5 own patches[set_off[i], set_off[i + 1]) and the other kinds own nothing.
 // Without set sites every head-set table is empty and no launch is added.
 static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32_t n_sites,
                       const int32_t* set_off, const tvr_head_patch* patches, const float* vectors,
@@ -2230,12 +2308,19 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
           return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": resid patch out of range");
         entry[i] = s.layer; p0[i] = s.pos; nrow[i] = T - s.pos;
         break;
+      case TVR_SITE_SET_RESID_PRE_VEC:  // planned as SET_RESID_PRE_POS; the row comes from `vectors`
+        if (s.layer < 0 || s.layer >= L || s.pos < 0 || s.pos >= T)
+          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": resid patch out of range");
+        if (!vectors || s.vec < 0 || s.vec >= n_vectors)
+          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": vector out of range");
+        entry[i] = s.layer; p0[i] = s.pos; nrow[i] = T - s.pos;
+        break;
       default:
         return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": unknown kind");
     }
   }
   // every site computes one row (its last position: ADD_ATTN_OUT_LASTPOS,
-  // NONE, a SET_RESID_PRE_POS of the last position): the site sequences go to
+  // NONE, a SET_RESID_PRE_POS / SET_RESID_PRE_VEC of the last position): the site sequences go to
   // the single-query attention kernel
   bool single_rows = true;
   for (int i = 0; i < n_sites; ++i) single_rows = single_rows && nrow[i] == 1;
@@ -2305,7 +2390,8 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
                                   : SeqDesc{Rc + row0[i], nrow[i], p0[i], srow, 0, 0};
     EntryDesc e{};
     // a head-set site enters as a plain copy of its clean rows (the entry kernel's TVR_SITE_NONE path)
-    e.kind = s.kind >= TVR_SITE_REPLACE_HEADSET_ALLPOS ? (int32_t)TVR_SITE_NONE : s.kind;
+    const bool set_kind = s.kind == TVR_SITE_REPLACE_HEADSET_ALLPOS || s.kind == TVR_SITE_REPLACE_HEADSET_LASTPOS;
+    e.kind = set_kind ? (int32_t)TVR_SITE_NONE : s.kind;
     e.row0 = Rc + row0[i];
     e.n = nrow[i];
     e.p0 = p0[i];

@@ -37,10 +37,10 @@ struct EntryDesc {
   int32_t n;          // rows
   int32_t p0;         // first position
   int32_t src_row;    // trace row of position 0 of `seq`
-  int32_t src2_row;   // SET_RESID: trace row supplying the patched position
-  int32_t patch_pos;  // SET_RESID: absolute patched position
+  int32_t src2_row;   // SET_RESID_PRE_POS: trace row supplying the patched position
+  int32_t patch_pos;  // SET_RESID_PRE_POS / _VEC: absolute patched position
   int32_t head;       // REPLACE_HEAD
-  int32_t vec;        // vector row
+  int32_t vec;        // vector row (SET_RESID_PRE_VEC: the row written at patch_pos)
   int32_t pad;
 };
 
@@ -341,9 +341,10 @@ entry_kernel(const EntryDesc* __restrict__ ents, const float* __restrict__ snap,
 #pragma unroll
     for (int u = 0; u < B; ++u) {
       const int pos = e.p0 + min(i0 + u, e.n - 1);
-      // NONE / SET_RESID_PRE_POS copy rows, one of them from another run
+      // NONE / SET_RESID_PRE_POS / SET_RESID_PRE_VEC copy rows, one of them from another run or from the
+      // caller's vectors (read element-wise: any float-aligned base)
       const int srow = (e.kind == 3 && pos == e.patch_pos) ? e.src2_row : e.src_row + pos;
-      v[u] = snap[(size_t)srow * d + c];
+      v[u] = (e.kind == 6 && pos == e.patch_pos) ? vectors[(size_t)e.vec * d + c] : snap[(size_t)srow * d + c];
     }
 #pragma unroll
     for (int u = 0; u < B; ++u)
@@ -395,6 +396,89 @@ __global__ void capture_finish_kernel(const float* __restrict__ partial,
   float s = 0.f;
   for (int g = 0; g < CAP_GROUPS; ++g) s += partial[(size_t)g * d + c];
   zsum[(size_t)l * d + c] += s;
+}
+
+// ---------------------------------------------------------------------------
+// Grouped residual capture (tvr_trace_capture_resid): out[g][l][:] += the sum
+// of hook_resid_pre[l] at one chosen row per sequence of group g, for every
+// l in [0, L] in one launch pair (blockIdx.y = layer; layer l's rows at
+// resid + l * lstride).  The host sorts the sequences by group (stable) into
+// `rows` and cuts each group into chunks of <= RESID_CAP_CHUNK consecutive
+// rows: the order of every sum is a function of the group's list alone.
+//   pass 1  one wave per (chunk, layer): the chunk's rows summed in order into
+//           the wave's LDS row (each lane owns its own columns: no barrier).
+//           A chunk that is its group's only one adds its sum to `out`
+//           (slot < 0), any other stores it to partial[l][slot].
+//   pass 2  per group of several chunks: out += its chunks' partials, in order.
+// CENTRE (a trace filled on the exact-fp16 path): each row's mean is removed
+// first, computed as center_rows_kernel<true> computes it (same lane
+// partition, same order), so the summands are the values tvr_trace_read
+// exports, bit for bit.  d % 4 == 0 (the trace rows are 16-B aligned); out is
+// read and written element-wise (float alignment).
+constexpr int RESID_CAP_CHUNK = 16;
+struct ResidCapChunk {
+  int32_t row0;   // first entry of `rows`
+  int32_t n;      // rows in the chunk (1 .. RESID_CAP_CHUNK)
+  int32_t group;  // output group
+  int32_t slot;   // partial slot, or -1: the group's only chunk, summed into out
+};
+struct ResidCapFinish {
+  int32_t group;
+  int32_t slot0;  // first partial slot of the group's chunks
+  int32_t n;      // chunks (>= 2)
+  int32_t pad;
+};
+
+template <bool CENTRE>
+__global__ void __launch_bounds__(64)
+resid_capture_partial_kernel(const float* __restrict__ resid, size_t lstride,
+                             const int32_t* __restrict__ rows,
+                             const ResidCapChunk* __restrict__ chunks, int n_slots,
+                             float* __restrict__ partial, float* __restrict__ out, int n_layers1, int d) {
+  extern __shared__ __attribute__((aligned(16))) float acc[];  // [d]
+  const ResidCapChunk ch = chunks[blockIdx.x];
+  const int l = blockIdx.y, lane = threadIdx.x, d4 = d >> 2;
+  const float* base = resid + (size_t)l * lstride;
+  float4* acc4 = (float4*)acc;
+  for (int c = lane; c < d4; c += 64) acc4[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = 0; i < ch.n; ++i) {
+    const float4* x = (const float4*)(base + (size_t)rows[ch.row0 + i] * d);
+    float mean = 0.f;
+    if constexpr (CENTRE) {
+      float s = 0.f;
+      for (int c = lane; c < d4; c += 64) {
+        const float4 v = x[c];
+        s += (v.x + v.y) + (v.z + v.w);
+      }
+      mean = wave_sum(s) / (float)d;
+    }
+    for (int c = lane; c < d4; c += 64) {
+      const float4 v = x[c];
+      float4 a = acc4[c];
+      a.x += v.x - mean; a.y += v.y - mean; a.z += v.z - mean; a.w += v.w - mean;
+      acc4[c] = a;
+    }
+  }
+  if (ch.slot >= 0) {
+    float4* p = (float4*)(partial + ((size_t)l * n_slots + ch.slot) * d);
+    for (int c = lane; c < d4; c += 64) p[c] = acc4[c];
+  } else {
+    __syncthreads();  // element c below was summed by another lane (one wave: the barrier only orders LDS)
+    float* o = out + ((size_t)ch.group * n_layers1 + l) * d;
+    for (int c = lane; c < d; c += 64) o[c] += acc[c];
+  }
+}
+
+__global__ void resid_capture_finish_kernel(const float* __restrict__ partial, int n_slots,
+                                            const ResidCapFinish* __restrict__ fins,
+                                            float* __restrict__ out, int n_layers1, int d) {
+  const int c = blockIdx.y * blockDim.x + threadIdx.x, l = blockIdx.z;
+  if (c >= d) return;
+  const ResidCapFinish f = fins[blockIdx.x];
+  const float* p = partial + ((size_t)l * n_slots + f.slot0) * d + c;
+  float s = 0.f;
+  for (int j = 0; j < f.n; ++j) s += p[(size_t)j * d];
+  out[((size_t)f.group * n_layers1 + l) * d + c] += s;
 }
 
 // out[l][h][c] = sum_k zsum[l][h*dh + k] * w2_l[c][h*dh + k]

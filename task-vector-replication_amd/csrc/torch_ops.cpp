@@ -9,6 +9,7 @@
 //   tvr::patch_sweep_sets tvr_patch_sweep_sets           (several scratch2.py:188 hooks in one run_with_hooks)
 //   tvr::project_heads   tvr_project_heads               (scratch2.py:97-98)
 //   tvr::forward_logits  tvr_forward_logits              (scratch.py:143,206,209)
+//   tvr::capture_resid   tvr_trace_capture_resid         (run_with_cache + hook_resid_pre[l][0, pos], summed)
 //
 // Every op enqueues on torch's CURRENT stream of the output device and
 // allocates its outputs through torch's caching allocator; host arrays
@@ -198,6 +199,28 @@ at::Tensor forward_logits(int64_t model, const std::optional<at::Tensor>& tokens
   return out;
 }
 
+// out [n_groups, L + 1, d] += the grouped sums of hook_resid_pre rows (tvr_trace_capture_resid).  pos / groups:
+// CPU int32 [n_seq] or None; out: a contiguous fp32 device tensor (an offset view is fine: float alignment
+// suffices), whose size the façade checks against the trace's model.  Returns out.
+at::Tensor& capture_resid(int64_t trace, const std::optional<at::Tensor>& pos, const std::optional<at::Tensor>& groups,
+                          int64_t n_groups, int64_t n_seq, at::Tensor& out) {
+  TORCH_CHECK_VALUE(trace != 0, "tvr: capture_resid needs a trace");
+  TORCH_CHECK_VALUE(n_groups > 0, "tvr: n_groups must be positive");
+  TORCH_CHECK_VALUE(!pos.has_value() || pos->numel() == n_seq, "tvr: pos must have one entry per traced sequence");
+  TORCH_CHECK_VALUE(!groups.has_value() || groups->numel() == n_seq,
+                    "tvr: groups must have one entry per traced sequence");
+  const c10::Device dev = out.device();
+  need_gpu(dev);
+  TORCH_CHECK_VALUE(out.scalar_type() == at::kFloat && out.is_contiguous() && out.dim() == 3 && out.size(0) == n_groups,
+                    "tvr: out must be a contiguous fp32 tensor [n_groups, n_layers + 1, d_model]");
+  DeviceGuard guard(dev);
+  check(tvr_trace_capture_resid(reinterpret_cast<tvr_trace*>(static_cast<intptr_t>(trace)), opt_host_i32(pos, "pos"),
+                                opt_host_i32(groups, "groups"), (int32_t)n_groups, out.data_ptr<float>(),
+                                cur_stream(dev)),
+        "tvr_trace_capture_resid");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tvr, m) {
@@ -211,6 +234,7 @@ TORCH_LIBRARY(tvr, m) {
   m.def("project_heads(int model, Tensor zsum, int n_heads) -> Tensor");
   m.def("forward_logits(int model, Tensor? tokens, Tensor? resid, int start_layer, Tensor seq_lens, int d_vocab, "
         "Device device) -> Tensor");
+  m.def("capture_resid(int trace, Tensor? pos, Tensor? groups, int n_groups, int n_seq, Tensor(a!) out) -> Tensor(a!)");
 }
 
 // Mixed host / device tensor arguments: one implementation for every backend key.
@@ -220,4 +244,5 @@ TORCH_LIBRARY_IMPL(tvr, CompositeExplicitAutograd, m) {
   m.impl("patch_sweep_sets", &patch_sweep_sets);
   m.impl("project_heads", &project_heads);
   m.impl("forward_logits", &forward_logits);
+  m.impl("capture_resid", &capture_resid);
 }

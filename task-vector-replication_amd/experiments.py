@@ -21,6 +21,13 @@ hook per head of a set; the function-vector paper's joint mean-ablation):
 
   joint_head_patch_effect, head_ablation_curve
 
+and Hendel et al.'s residual-stream task vectors (mean of hook_resid_pre at the
+function token over ICL prompts, written into a zero-shot prompt's last
+position layer by layer):
+
+  extract_task_vectors, apply_task_vectors_to_zero_shot,
+  apply_task_vectors_to_zero_shot_by_probability
+
 Drop-in notes
 * ``model`` is an ``amd.Model`` instead of a HookedTransformer; it must be
   passed (the reference's defaults bind a module-global model).
@@ -100,10 +107,13 @@ def _layer_vectors(layered_vectors: torch.Tensor, model: Model, late_binding: bo
 
 
 def _add_site_outputs(model: Model, seqs: List[List[int]], site_seq, site_layer, site_vec, vectors: torch.Tensor,
-                      targets: Optional[List[int]], topk: int, shard=None, clean_outputs: bool = True):
-    """Clean forward of ``seqs`` + the ADD_ATTN_OUT_LASTPOS sites
+                      targets: Optional[List[int]], topk: int, shard=None, clean_outputs: bool = True,
+                      kind: int = _lib.SITE_ADD_ATTN_OUT_LASTPOS):
+    """Clean forward of ``seqs`` + the last-position vector sites of the global
+    site list (site_seq, site_layer, site_vec).  ``kind``: ADD_ATTN_OUT_LASTPOS
     (``hook_attn_out[0, -1] += vectors[vec]`` at ``layer``, scratch2.py:107-109)
-    of the global site list (site_seq, site_layer, site_vec).  ``shard``
+    or SET_RESID_PRE_VEC (``hook_resid_pre[0, -1] = vectors[vec]`` at ``layer``,
+    then the forward from that layer: Hendel et al.'s task-vector patch).  ``shard``
     (distributed.SiteShard) evaluates only this rank's sites and all-gathers
     the per-site outputs, so every rank returns every site in global order.
     ``clean_outputs=False``: the caller reads no clean outputs, so the clean
@@ -124,10 +134,12 @@ def _add_site_outputs(model: Model, seqs: List[List[int]], site_seq, site_layer,
     if len(sel):
         patched = {k: [] for k in patched}
         sites = make_sites(len(sel))
-        sites["kind"] = _lib.SITE_ADD_ATTN_OUT_LASTPOS
+        sites["kind"] = kind
         sites["seq"] = np.asarray(site_seq)[sel]
         sites["layer"] = np.asarray(site_layer)[sel]
         sites["vec"] = np.asarray(site_vec)[sel]
+        if kind == _lib.SITE_SET_RESID_PRE_VEC:  # the patched position: the last one
+            sites["pos"] = np.asarray([len(s) for s in seqs], dtype=np.int32)[sites["seq"]] - 1
         if targets is not None:
             sites["target"] = np.asarray(targets)[sites["seq"]]
         for a, b in _chunks(len(sites), MAX_SITES_PER_LAUNCH):
@@ -142,25 +154,27 @@ def _add_site_outputs(model: Model, seqs: List[List[int]], site_seq, site_layer,
 
 def _injection_sweep(model: Model, seqs: List[List[int]], vectors: torch.Tensor, vec_of_layer,
                      layers: Sequence[int], targets: Optional[List[int]], topk: int, shard=None,
-                     clean_outputs: bool = True):
-    """One ADD_ATTN_OUT_LASTPOS site per (prompt, layer).  Returns (clean
-    outputs, patched outputs [n, len(layers)])."""
+                     clean_outputs: bool = True, kind: int = _lib.SITE_ADD_ATTN_OUT_LASTPOS):
+    """One last-position site of ``kind`` (``_add_site_outputs``) per (prompt,
+    layer).  Returns (clean outputs, patched outputs [n, len(layers)])."""
     n, layers = len(seqs), list(layers)
     site_layer = np.tile(np.asarray(layers, dtype=np.int32), n)
     site_vec = np.tile(np.asarray([vec_of_layer(l) for l in layers], dtype=np.int32), n)
     clean, patched = _add_site_outputs(model, seqs, np.repeat(np.arange(n, dtype=np.int32), len(layers)), site_layer,
-                                       site_vec, vectors, targets, topk, shard, clean_outputs)
+                                       site_vec, vectors, targets, topk, shard, clean_outputs, kind)
     return clean, {k: v.view(n, len(layers), *v.shape[1:]) for k, v in patched.items()}
 
 
 @range_checked
 def _zero_shot_accuracy(layered_vectors, contexts: Pairs, function_token: str, model: Model,
-                        reference_late_binding: bool, shard=None) -> List[float]:
+                        reference_late_binding: bool, shard=None,
+                        kind: int = _lib.SITE_ADD_ATTN_OUT_LASTPOS) -> List[float]:
     L = model.cfg.n_layers
     vectors, vec_of = _layer_vectors(layered_vectors, model, reference_late_binding)
     f = model.to_single_token(function_token)
     seqs = [[0, model.to_single_token(x), f] for x, _ in contexts]
-    _, patched = _injection_sweep(model, seqs, vectors, vec_of, range(L), None, 1, shard, clean_outputs=False)
+    _, patched = _injection_sweep(model, seqs, vectors, vec_of, range(L), None, 1, shard, clean_outputs=False,
+                                  kind=kind)
     # top-1 decoded == answer (scratch2.py's to_string comparison), decoding
     # each distinct token id once instead of once per (prompt, layer)
     ids, inv = np.unique(patched["topk"][..., 0].cpu().numpy(), return_inverse=True)
@@ -174,14 +188,15 @@ def _zero_shot_accuracy(layered_vectors, contexts: Pairs, function_token: str, m
 
 @range_checked
 def _zero_shot_dprob(layered_vectors, contexts: Pairs, function_token: str, model: Model,
-                     reference_late_binding: bool, shard=None) -> torch.Tensor:
+                     reference_late_binding: bool, shard=None,
+                     kind: int = _lib.SITE_ADD_ATTN_OUT_LASTPOS) -> torch.Tensor:
     L = model.cfg.n_layers
     vectors, vec_of = _layer_vectors(layered_vectors, model, reference_late_binding)
     f = model.to_single_token(function_token)
     enc = model.tokenizer.encode
     seqs = [[0] + enc(x) + [f] for x, _ in contexts]
     targets = [enc(y)[0] for _, y in contexts]
-    clean, patched = _injection_sweep(model, seqs, vectors, vec_of, range(L), targets, 0, shard)
+    clean, patched = _injection_sweep(model, seqs, vectors, vec_of, range(L), targets, 0, shard, kind=kind)
     return (patched["prob"] - clean["prob"][:, None]).sum(0) / len(contexts)
 
 
@@ -200,6 +215,61 @@ def apply_layered_vectors_to_zero_shot_by_probability(layered_vectors: torch.Ten
     """Per-layer mean change of the first answer token's probability
     (patched − clean), [n_layers] on the device."""
     return _zero_shot_dprob(layered_vectors, contexts, function_token, model, reference_late_binding)
+
+
+# ------------------------------------------------- residual-stream task vectors
+def _task_vector_rows(task_vectors: torch.Tensor, cfg) -> torch.Tensor:
+    """Rows 0..L-1 of a [L, d] or [L + 1, d] task-vector table (row l is
+    written into ``hook_resid_pre[l]``; ``extract_task_vectors``' row L, the
+    final residual, has no block to enter).  No engine call."""
+    if not isinstance(task_vectors, torch.Tensor) or task_vectors.dim() != 2 or \
+            task_vectors.shape[0] not in (cfg.n_layers, cfg.n_layers + 1) or task_vectors.shape[1] != cfg.d_model:
+        raise ValueError("task_vectors must be of shape (n_layers, d_model) or (n_layers + 1, d_model)")
+    return task_vectors[:cfg.n_layers]
+
+
+@range_checked
+def extract_task_vectors(contexts: Pairs, function_token: str, model: Model = None, num_contexts: int = 1024,
+                         len_contexts: int = 4, seperator_token: Optional[str] = None) -> torch.Tensor:
+    """Hendel et al.'s task vectors θ(l): the mean over ``num_contexts`` ICL
+    prompts (the prompt stream of ``generate_mean_activation``) of
+    ``blocks.{l}.hook_resid_pre`` at the last position — the function token of
+    the query — for every layer; row L is the final residual.  [L + 1, d] on
+    the device.  One clean forward into a trace and one grouped capture
+    (``Model.capture_resid``) per ``EXTRACT_BATCH`` prompts."""
+    if num_contexts <= 0:
+        raise ValueError("num_contexts must be positive")
+    if len_contexts < 0 or len_contexts >= len(contexts):
+        raise ValueError("len_contexts must be smaller than the number of contexts (demos + one query)")
+    prompts = sample_icl_prompts(model, contexts, function_token, seperator_token, num_contexts, len_contexts)
+    total = None
+    for a, b in _chunks(len(prompts), EXTRACT_BATCH):
+        seqs = prompts[a:b]
+        trace = model._sweep_trace(len(seqs), sum(len(s) for s in seqs))
+        model.forward_clean(seqs, trace=trace)
+        total = model.capture_resid(trace, out=total)  # accumulates across the chunks, in chunk order
+    return total[0] / num_contexts
+
+
+@range_checked
+def apply_task_vectors_to_zero_shot(task_vectors: torch.Tensor, contexts: Pairs, function_token: str,
+                                    model: Model = None) -> List[float]:
+    """Per-layer top-1 accuracy of zero-shot ``[BOS, x, f]`` prompts with
+    ``task_vectors[l]`` written into ``hook_resid_pre[l][0, -1]`` and the
+    forward continued from layer l (Hendel et al.'s patch).  One deferred clean
+    forward + one SET_RESID_PRE_VEC site per (prompt, layer)."""
+    rows = _task_vector_rows(task_vectors, model.cfg)
+    return _zero_shot_accuracy(rows, contexts, function_token, model, False, kind=_lib.SITE_SET_RESID_PRE_VEC)
+
+
+@range_checked
+def apply_task_vectors_to_zero_shot_by_probability(task_vectors: torch.Tensor, contexts: Pairs, function_token: str,
+                                                   model: Model = None) -> torch.Tensor:
+    """Per-layer mean change of the first answer token's probability (patched
+    − clean) under the same patch, prompts ``[BOS] + enc(x) + [f]``.
+    [n_layers] on the device."""
+    rows = _task_vector_rows(task_vectors, model.cfg)
+    return _zero_shot_dprob(rows, contexts, function_token, model, False, kind=_lib.SITE_SET_RESID_PRE_VEC)
 
 
 # ------------------------------------------------------------------- a6 / a7

@@ -7,7 +7,9 @@ token helpers, and drives the engine's batched entry points:
   per-prompt ``forward`` / ``run_with_cache`` calls);
 * ``patch_sweep``    — many (prompt, patch site) pairs in one staircase
   launch sequence (replaces the per-site ``run_with_hooks`` loops);
-* ``project_heads``  — z-form capture → ``hook_result`` form.
+* ``project_heads``  — z-form capture → ``hook_result`` form;
+* ``capture_resid``  — grouped sums of ``hook_resid_pre`` rows of a trace, every
+  layer at once (replaces ``run_with_cache`` + a Python mean over prompts).
 
 The compute entry points run as torch.library operators (``torch.ops.tvr.*``,
 csrc/torch_ops.cpp over the C ABI) on torch's current stream, with outputs
@@ -511,6 +513,51 @@ class Model(TokenizerMixin):
             out["topk"] = top
         if return_logits:
             out["logits"] = logits
+        return out
+
+    def capture_resid(self, trace: Trace, positions: Optional[Sequence[int]] = None,
+                      groups: Optional[Sequence[int]] = None, n_groups: int = 1,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Grouped sums of residual-stream rows of ``trace``
+        (tvr_trace_capture_resid): ``[n_groups, L + 1, d]`` with
+        ``[g, l] = Σ_{s: groups[s] == g} blocks.{l}.hook_resid_pre[s][positions[s]]``
+        (row ``L``: the final residual), TransformerLens' centred values.
+        ``positions`` defaults to every sequence's last position, ``groups`` to
+        one group; ``groups = range(n)`` with ``n_groups = n`` gives per-prompt
+        vectors.  Returns a fresh zeroed tensor with the sums, or ``out``
+        (contiguous fp32 on the model device, that shape) with the sums ADDED
+        to it.  Bitwise reproducible for a given trace."""
+        if trace.model is not self:
+            raise ValueError("trace belongs to another model")
+        n = len(trace.seq_lens)
+        if n == 0:
+            raise ValueError("trace is empty: run forward_clean(trace=...) first")
+        n_groups = int(n_groups)
+        if n_groups <= 0:
+            raise ValueError("n_groups must be positive")
+        pos = grp = None
+        if positions is not None:
+            pos = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1)
+            if pos.shape[0] != n:
+                raise ValueError("positions must have one entry per traced sequence")
+            if np.any(pos < 0) or np.any(pos >= np.asarray(trace.seq_lens)):
+                raise ValueError("a position lies outside its sequence")
+        if groups is not None:
+            grp = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+            if grp.shape[0] != n:
+                raise ValueError("groups must have one entry per traced sequence")
+            if np.any(grp < 0) or np.any(grp >= n_groups):
+                raise ValueError("a group lies outside [0, n_groups)")
+        shape = (n_groups, self.cfg.n_layers + 1, self.cfg.d_model)
+        if out is None:
+            out = torch.zeros(shape, device=self.device)
+        elif (tuple(out.shape) != shape or out.device != self.device or out.dtype != torch.float32
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous fp32 tensor {shape} on the model device")
+        self._op("capture_resid", trace._h.value, torch.from_numpy(pos) if pos is not None else None,
+                 torch.from_numpy(grp) if grp is not None else None, n_groups, n, out)
+        self._check_range("tvr_trace_capture_resid")  # (a deferred clean forward may have run)
+        trace._pending_out = None
         return out
 
     def project_heads(self, zsum: torch.Tensor) -> torch.Tensor:
