@@ -34,6 +34,7 @@
 #include "lin_entry.hpp"
 #include "entry_mfma.hpp"
 #include "headset_patch.hpp"
+#include "sweep_plan.hpp"
 
 using namespace tvr;
 
@@ -1964,6 +1965,29 @@ int tvr_trace_capture_resid(tvr_trace* t, const int32_t* pos, const int32_t* gro
 }  // extern "C"
 
 namespace {
+// The checks tvr_forward_clean and its deferred form share: off[s] the first row of sequence s, R the rows.
+// tokens may be null (a residual input); trace null: no capacity to check.
+int check_seqs(const tvr_config& c, const tvr_trace* trace, const int32_t* tokens, const int32_t* seq_lens,
+               int n_seq, std::vector<int>& off, int& R) {
+  off.resize(n_seq);
+  R = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    const int T = seq_lens[s];
+    if (T <= 0) return fail(TVR_ERR_INVALID, "sequence " + std::to_string(s) + " is empty");
+    if (T > c.n_ctx)
+      return fail(TVR_ERR_UNSUPPORTED, "sequence length " + std::to_string(T) + " exceeds n_ctx " +
+                                           std::to_string(c.n_ctx));
+    off[s] = R;
+    R += T;
+  }
+  for (int r = 0; tokens && r < R; ++r)
+    if (tokens[r] < 0 || tokens[r] >= c.d_vocab)
+      return fail(TVR_ERR_INVALID, "token id " + std::to_string(tokens[r]) + " out of range");
+  if (trace && (n_seq > trace->max_seqs || R > trace->max_tokens))
+    return fail(TVR_ERR_INVALID, "trace capacity exceeded");
+  return TVR_OK;
+}
+
 // The batched clean forward behind tvr_forward_clean / tvr_forward_logits.
 //   tokens     host ids (embedded), or nullptr with resid_in: device [R][d]
 //              hook_resid_pre of start_layer (TL forward(resid, start_at_layer=))
@@ -1982,24 +2006,13 @@ int forward_impl(tvr_model* m, tvr_trace* trace, const int32_t* tokens, const fl
   hipStream_t st = (hipStream_t)stream;
   const tvr_config& c = m->cfg;
   const int d = c.d_model, L = c.n_layers;
-  std::vector<int32_t> off(n_seq), last(n_seq);
+  std::vector<int32_t> off, last(n_seq);
   int R = 0, maxT = 0;
+  TVR_TRY(check_seqs(c, trace, tokens, seq_lens, n_seq, off, R));
   for (int s = 0; s < n_seq; ++s) {
-    const int T = seq_lens[s];
-    if (T <= 0) return fail(TVR_ERR_INVALID, "sequence " + std::to_string(s) + " is empty");
-    if (T > c.n_ctx)
-      return fail(TVR_ERR_UNSUPPORTED, "sequence length " + std::to_string(T) + " exceeds n_ctx " +
-                                           std::to_string(c.n_ctx));
-    off[s] = R;
-    last[s] = R + T - 1;
-    R += T;
-    maxT = std::max(maxT, T);
+    last[s] = off[s] + seq_lens[s] - 1;
+    maxT = std::max(maxT, seq_lens[s]);
   }
-  for (int r = 0; tokens && r < R; ++r)
-    if (tokens[r] < 0 || tokens[r] >= c.d_vocab)
-      return fail(TVR_ERR_INVALID, "token id " + std::to_string(tokens[r]) + " out of range");
-  if (trace && (n_seq > trace->max_seqs || R > trace->max_tokens))
-    return fail(TVR_ERR_INVALID, "trace capacity exceeded");
   if (trace) trace->uncentred = use_x16(m);
 
   std::vector<SeqDesc> seqs(n_seq);
@@ -2019,16 +2032,8 @@ int forward_impl(tvr_model* m, tvr_trace* trace, const int32_t* tokens, const fl
     for (int s = 0; s < n_seq; ++s) {
       const int T = seq_lens[s];
       const int32_t* tk = tokens + off[s];
-      int P = 0, ld = -1;
-      const auto it = first.find(tk[0]);
-      if (it == first.end()) {
-        first.emplace(tk[0], s);
-      } else {
-        ld = it->second;
-        const int32_t* tl = tokens + off[ld];
-        const int cap = std::min(T - 1, seq_lens[ld]);
-        while (P < cap && tk[P] == tl[P]) ++P;
-      }
+      const int ld = first.emplace(tk[0], s).first->second;  // (s itself: the first prompt with this token)
+      const int P = ld == s ? 0 : shared_prefix_len(tk, T, tokens + off[ld], seq_lens[ld]);
       seqs[s] = P > 0 ? SeqDesc{Rc, T - P, P, seqs[ld].row0, 0, 1} : SeqDesc{Rc, T, 0, -1, 0, 0};
       ctok.insert(ctok.end(), tk + P, tk + T);
       last[s] = Rc + T - P - 1;
@@ -2176,22 +2181,9 @@ int tvr_forward_clean_deferred(tvr_model* m, tvr_trace* trace, const int32_t* to
   if (topk < 0 || topk > STATS_MAX_K) return fail(TVR_ERR_INVALID, "topk must be in [0, 16]");
   if (topk > 0 && !out_topk) return fail(TVR_ERR_INVALID, "topk > 0 needs out_topk");
   TVR_TRY(flush_pending(trace, stream));
-  const tvr_config& c = m->cfg;
-  std::vector<int> off(n_seq);
+  std::vector<int> off;
   int R = 0;
-  for (int s = 0; s < n_seq; ++s) {
-    const int T = seq_lens[s];
-    if (T <= 0) return fail(TVR_ERR_INVALID, "sequence " + std::to_string(s) + " is empty");
-    if (T > c.n_ctx)
-      return fail(TVR_ERR_UNSUPPORTED, "sequence length " + std::to_string(T) + " exceeds n_ctx " +
-                                           std::to_string(c.n_ctx));
-    off[s] = R;
-    R += T;
-  }
-  for (int r = 0; r < R; ++r)
-    if (tokens[r] < 0 || tokens[r] >= c.d_vocab)
-      return fail(TVR_ERR_INVALID, "token id " + std::to_string(tokens[r]) + " out of range");
-  if (n_seq > trace->max_seqs || R > trace->max_tokens) return fail(TVR_ERR_INVALID, "trace capacity exceeded");
+  TVR_TRY(check_seqs(m->cfg, trace, tokens, seq_lens, n_seq, off, R));
   trace->seq_off = off;
   trace->seq_len.assign(seq_lens, seq_lens + n_seq);
   trace->tokens.assign(tokens, tokens + R);
@@ -2216,6 +2208,181 @@ int tvr_forward_logits(tvr_model* m, const int32_t* tokens, const float* resid_i
 
 
 
+// What the sweep's per-layer launches read: the plan, its tables in the workspace and the lin-entry scratch.
+struct SweepCtx {
+  tvr_model* m;
+  tvr_trace* trace;
+  const SweepPlan& p;
+  bool fused;
+  Acts& a;
+  const float* vectors;
+  hipStream_t st;
+  const SeqDesc* seqs;
+  const EntryDesc* ents;
+  const int32_t* egidx;
+  const EntryGroup* egroups;
+  const LinRow* lin_rows;
+  const LinMB* lin_mbs;
+  const int32_t* lin_vids;
+  float2* lnstats;
+  float* raw_h;
+  uint16_t* vact;  // vectors in the activation format
+  float* g;
+  uint16_t* vg;  // exact-fp16 weights: one layer's G rows (centred vectors x LN1 / LN2 gamma, activation format)
+};
+
+// The sites entering at layer l (L: the final norm's input) materialise their residual rows.
+static int sweep_enter(const SweepCtx& cx, int l) {
+  tvr_model* m = cx.m;
+  const SweepPlan& p = cx.p;
+  const tvr_config& c = m->cfg;
+  const int d = c.d_model, k0 = l > 0 ? p.cnt_le[l - 1] : 0, k1 = p.cnt_le[l];
+  if (k1 <= k0) return TVR_OK;
+  const size_t tstride = (size_t)cx.trace->max_tokens * d;
+  // the clean rows' hook_resid_pre: the live rows [0, Rc) in a fused sweep (the trace's copy is written by
+  // this layer's LayerNorm, after the entry), else the trace
+  const float* snap = cx.fused ? cx.a.resid : cx.trace->resid + (size_t)l * tstride;
+  const float* zsnap = l > 0 ? cx.trace->z + (size_t)(l - 1) * tstride : nullptr;
+  const float* w2 = l > 0 ? m->layers[l - 1].w2 : nullptr;
+  const dim3 eg(k1 - k0, (d + ENTRY_THREADS - 1) / ENTRY_THREADS);
+  ProfSpan ps(m, cx.st);
+  const bool mf = p.eg_cnt[l] > 0 && (c.d_head == 16 || c.d_head == 64 || c.d_head == 80 || c.d_head == 128);
+  if (mf) {
+    const dim3 gg(p.eg_cnt[l], (d + ENTRY_COLS - 1) / ENTRY_COLS);
+#define TVR_ENTRY_MF(DH)                                                                                     \
+  hipLaunchKernelGGL(entry_replace_mfma_kernel<DH>, gg, dim3(ENTRY_THREADS), 0, cx.st, cx.ents, cx.egidx,     \
+                     cx.egroups + p.eg_beg[l], snap, zsnap, w2, m->K2, cx.vectors, cx.a.resid, d)
+    switch (c.d_head) {
+      case 16: TVR_ENTRY_MF(16); break;
+      case 64: TVR_ENTRY_MF(64); break;
+      case 80: TVR_ENTRY_MF(80); break;
+      default: TVR_ENTRY_MF(128); break;
+    }
+#undef TVR_ENTRY_MF
+    TVR_HIP(hipGetLastError());
+  }
+  if (p.ent_other[l] || !mf) {
+    const size_t zbytes = mf ? 0 : (size_t)std::min(p.maxT, ENTRY_LDS_POS) * c.d_head * sizeof(float);
+    if (zbytes > 64 * 1024)
+      TVR_HIP(hipFuncSetAttribute((const void*)entry_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)zbytes));
+    hipLaunchKernelGGL(entry_kernel, eg, dim3(ENTRY_THREADS), zbytes, cx.st, cx.ents + k0, snap, zsnap, w2, m->K2,
+                       cx.vectors, cx.a.resid, d, c.d_head, mf ? 1 : 0);
+    TVR_HIP(hipGetLastError());
+  }
+  ps.done(TVR_HBM_ENTRY, p.entry_bytes[l]);
+  return TVR_OK;
+}
+
+// Layer l's block with the linearised entry rows [Rp, Rl) (p.use_lin[l])
+static int sweep_block_lin(const SweepCtx& cx, int l, int Rl, const float* cache, float* zf) {
+  tvr_model* m = cx.m;
+  const SweepPlan& p = cx.p;
+  Acts& a = cx.a;
+  hipStream_t st = cx.st;
+  const tvr_config& c = m->cfg;
+  const tvr_layer_weights& w = m->layers[l];
+  const int d = c.d_model, fmt = act_fmt(m), Rc = p.Rc, Rp = Rc + p.rows_le[l - 1], D1 = m->D1, nv = p.lin_nv[l];
+  const int32_t* vids = cx.lin_vids + p.lin_vid_off[l];
+  TVR_TRY(launch_lnpre(a.resid, d, nullptr, a.xn, d, Rl, d, c.ln_eps, a.fmt, st, m, cx.lnstats, a.resid_mirror,
+                       a.mirror_rows, a.xn2 ? m->g1[l] : nullptr, a.xn2 ? m->g2[l] : nullptr, a.xn2));
+  GemmEpi e1 = epi_qkv_mlpin(m, w.b1, a.qkv, a);
+  e1.raw = cx.raw_h;
+  e1.raw_rows = Rc;
+  e1.ld_raw = c.d_mlp;
+  TVR_TRY(launch_w1(m, l, a.xn, Rp, 0, D1, e1, st, a.xn2));
+  ProfSpan ps(m, st);
+  const bool prof = m->prof;
+  m->prof = false;  // G and the entry rows are timed as one HBM-kind span, not as GEMM-family launches
+  GemmEpi eg{};
+  eg.out0 = cx.g;
+  eg.ld0 = D1;
+  eg.a_rows = vids;
+  eg.skinny = 1;
+  int rc = TVR_OK;
+  const int nqk = fmt == ACT_BF16 && !m->w1qk.empty() ? 2 * d : 0;  // bf16: Q / K columns on fp16 operands
+  if (use_x16(m)) {
+    // G = v W1'^T on the raw fp16 W1 (one plane, 2 products): rows ((v - mean) o gamma1 | gamma2), lin_entry.hpp
+    uint16_t* vg1 = cx.vg;
+    uint16_t* vg2 = vg1 + (size_t)2 * nv * d;
+    hipLaunchKernelGGL(lin_gamma_rows_kernel, dim3((nv + 3) / 4), dim3(256), 0, st, cx.vectors, d, vids, m->g1[l],
+                       m->g2[l], vg1, vg2, nv, m->range_flag);
+    rc = hipGetLastError() == hipSuccess ? TVR_OK : fail(TVR_ERR_HIP, "lin_gamma_rows_kernel launch");
+    GemmEpi ex = eg;
+    ex.a_rows = nullptr;  // the rows are the layer's vectors in order
+    const int q = 3 * d;  // first MLP-in column: it and the columns after it read the gamma2 rows
+    if (rc == TVR_OK && q % 256 == 0) {
+      ex.a2 = vg2;
+      ex.a2_col = q;
+      rc = launch_gemm(EPI_BIAS, vg1, d, fmt, m->w1x[l], d, nv, D1, d, ex, st, m);
+    } else if (rc == TVR_OK) {  // two launches (d % 256 != 0: the tiny test model)
+      rc = launch_gemm(EPI_BIAS, vg1, d, fmt, m->w1x[l], d, nv, q, d, ex, st, m);
+      GemmEpi e2 = ex;
+      e2.out0 = ex.out0 + q;
+      if (rc == TVR_OK)
+        rc = launch_gemm(EPI_BIAS, vg2, d, fmt, m->w1x[l].rows((size_t)q * d), d, nv, D1 - q, d, e2, st, m);
+    }
+  } else if (nqk > 0) {
+    rc = launch_gemm(EPI_BIAS, cx.vact + d, d, ACT_F16, m->w1qk[l], d, nv, nqk, d, eg, st, m);
+    GemmEpi e2 = eg;
+    e2.out0 = eg.out0 + nqk;
+    if (rc == TVR_OK)
+      rc = launch_gemm(EPI_BIAS, cx.vact, d, fmt, m->w1[l].rows((size_t)nqk * d), d, nv, D1 - nqk, d, e2, st, m);
+  } else {
+    rc = launch_gemm(EPI_BIAS, cx.vact, d, fmt, m->w1[l], d, nv, D1, d, eg, st, m);
+  }
+  m->prof = prof;
+  TVR_TRY(rc);
+  const int npl = fmt == ACT_X2F16 ? 2 : 1, KP = m->lin_kp, nmb = p.lin_nmb[l];
+  const size_t per = (size_t)c.n_heads * D1 * KP;
+  const uint16_t* wp = m->lin_planes + (size_t)(l - 1) * npl * per;
+  // X2F16: every column tile in one launch; BF16: the Q / K column tiles [0, 2d) on the fp16 rows of the
+  // planes (scale lin_scale[l]), the rest on bf16
+  const int n_ct = (D1 + 255) / 256, ct_qk = fmt == ACT_BF16 ? lin_qk_cols(c) / 256 : 0;
+  float acc_scale = fmt == ACT_X2F16 ? 1.0f / (m->lin_scale[l] * X2_ASCALE) : 1.0f;
+  dim3 g;
+  int ct_base = 0;
+#define TVR_LIN(F, NK, ...)                                                                                          \
+  hipLaunchKernelGGL((lin_entry_kernel<F, NK __VA_OPT__(,) __VA_ARGS__>), g, dim3(LIN_THREADS), 0, st,                \
+                     cx.lin_mbs + p.lin_mb_off[l], nmb, cx.lin_rows, wp, per, acc_scale,                              \
+                     cx.trace->z + (size_t)(l - 1) * cx.trace->max_tokens * d, d, c.d_head, cx.lnstats, a.qkv,        \
+                     cx.raw_h, c.d_mlp, cx.g, m->lin_c1 + (size_t)l * D1, w.b1, D1,                                   \
+                     reinterpret_cast<uint16_t*>(a.a2) + act_col_rt(a.fmt, d), 2 * m->K2, m->K2, m->range_flag, ct_base)
+#define TVR_LIN_K(F, ...)                                                 \
+  if (KP == 32) TVR_LIN(F, 1 __VA_OPT__(,) __VA_ARGS__);                  \
+  else if (KP == 64) TVR_LIN(F, 2 __VA_OPT__(,) __VA_ARGS__);             \
+  else if (KP == 96) TVR_LIN(F, 3 __VA_OPT__(,) __VA_ARGS__);             \
+  else TVR_LIN(F, 4 __VA_OPT__(,) __VA_ARGS__)
+  if (fmt == ACT_X2F16 && a.fmt == ACT_X2F16I) {  // a2's GELU planes interleaved
+    g = dim3(nmb * n_ct);
+    TVR_LIN_K(ACT_X2F16, true);
+  } else if (fmt == ACT_X2F16) {
+    g = dim3(nmb * n_ct);
+    TVR_LIN_K(ACT_X2F16);
+  } else {
+    if (ct_qk > 0) {
+      g = dim3(nmb * ct_qk);
+      acc_scale = 1.0f / m->lin_scale[l];
+      TVR_LIN_K(ACT_F16);
+    }
+    g = dim3(nmb * (n_ct - ct_qk));
+    acc_scale = 1.0f;
+    ct_base = ct_qk;
+    TVR_LIN_K(ACT_BF16);
+  }
+#undef TVR_LIN_K
+#undef TVR_LIN
+  TVR_HIP(hipGetLastError());
+  // algorithmic bytes: the entering rows' outputs written and their clean rows' y_c read (4 B per
+  // column each), z slices, the layer's Wsc planes once, G written + read, the vectors' planes
+  ps.done(TVR_HBM_LIN_ENTRY, (double)p.lin_nrows[l] * (8.0 * D1 + 4.0 * c.d_head) + 2.0 * npl * per +
+                                 nv * (8.0 * D1 + 4.0 * d) + 2.0 * npl * (double)D1 * d);
+  ProfSpan pa(m, st);
+  TVR_TRY(launch_attention(m, a.qkv, cache, cx.seqs, p.nc + p.cnt_le[l], p.maxT, a.a2, a.fmt, zf, st, false, Rc));
+  pa.done(TVR_HBM_ATTENTION, attention_bytes(d, Rl, Rl, a.fmt, zf ? std::min(Rl, Rc) : 0));
+  return run_block_out(m, l, Rl, a, st);
+}
+
 // The body of tvr_patch_sweep and tvr_patch_sweep_sets.  set_off == nullptr: the plain sweep (kinds 0-3
 // and 6 only); else sites of kinds 4 / 5 own patches[set_off[i], set_off[i + 1]) and the other kinds own nothing.
 // Without set sites every head-set table is empty and no launch is added.
@@ -2231,7 +2398,7 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
   if (topk > 0 && !out_topk) return fail(TVR_ERR_INVALID, "topk > 0 needs out_topk");
   hipStream_t st = (hipStream_t)stream;
   const tvr_config& c = m->cfg;
-  const int d = c.d_model, L = c.n_layers;
+  const int d = c.d_model, L = c.n_layers, fmt = act_fmt(m);
   // Fused clean forward (a deferred tvr_forward_clean on this trace): the
   // clean rows [0, Rc) (trace row layout) run in the same launches as the
   // site rows, which follow them; the sites read the clean K/V from the live
@@ -2239,592 +2406,146 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
   // forward's own small-M launches (52 prompts x 3 tokens).
   const bool fused = trace->pending;
   if (fused) trace->uncentred = use_x16(m);  // this sweep fills the trace's clean rows
-  const int Rc = fused ? trace->n_tokens : 0, nc = fused ? trace->n_seq : 0;
 
-  // --- plan -----------------------------------------------------------------
-  std::vector<int> entry(n_sites), p0(n_sites), nrow(n_sites);
-  int maxT = 0;
-  for (int s = 0; s < nc; ++s) maxT = std::max(maxT, trace->seq_len[s]);
-  for (int i = 0; i < n_sites; ++i) {
-    const tvr_site& s = sites[i];
-    if (s.seq < 0 || s.seq >= trace->n_seq)
-      return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": seq out of range");
-    const int T = trace->seq_len[s.seq];
-    maxT = std::max(maxT, T);
-    const bool is_set = s.kind == TVR_SITE_REPLACE_HEADSET_ALLPOS || s.kind == TVR_SITE_REPLACE_HEADSET_LASTPOS;
-    if (is_set && !set_off)
-      return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": head-set kinds (4, 5) go through tvr_patch_sweep_sets");
-    if (set_off && !is_set && set_off[i + 1] != set_off[i])
-      return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": only head-set kinds (4, 5) own patches");
-    if (is_set) {
-      // Head-set site: enters at its lowest patched layer as an unpatched copy of the clean rows (the
-      // entry kernel's row copy) and runs every layer from there, patched by headset_patch_kernel at
-      // each layer where it has heads.  An empty set is TVR_SITE_NONE.
-      int l_min = L;
-      std::vector<std::pair<int, int>> lh;
-      for (int q = set_off[i]; q < set_off[i + 1]; ++q) {
-        const tvr_head_patch& hp = patches[q];
-        if (hp.layer < 0 || hp.layer >= L || hp.head < 0 || hp.head >= c.n_heads)
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": patch layer/head out of range");
-        if (!vectors || hp.vec < 0 || hp.vec >= n_vectors)
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": patch vector out of range");
-        l_min = std::min(l_min, (int)hp.layer);
-        lh.emplace_back(hp.layer, hp.head);
-      }
-      std::sort(lh.begin(), lh.end());
-      if (std::adjacent_find(lh.begin(), lh.end()) != lh.end())
-        return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": the same (layer, head) twice in one set");
-      entry[i] = l_min;
-      if (s.kind == TVR_SITE_REPLACE_HEADSET_ALLPOS && l_min < L) {
-        p0[i] = 0; nrow[i] = T;
-      } else {
-        p0[i] = T - 1; nrow[i] = 1;
-      }
-      continue;
-    }
-    switch (s.kind) {
-      case TVR_SITE_NONE:
-        entry[i] = L; p0[i] = T - 1; nrow[i] = 1;
-        break;
-      case TVR_SITE_REPLACE_HEAD_ALLPOS:
-        if (s.layer < 0 || s.layer >= L || s.head < 0 || s.head >= c.n_heads)
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": layer/head out of range");
-        if (!vectors || s.vec < 0 || s.vec >= n_vectors)
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": vector out of range");
-        if (set_off && ((uintptr_t)vectors & 15))  // tvr.h: the head-replacement entry kernels load 16 bytes
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": REPLACE_HEAD_ALLPOS needs 16-byte aligned vectors");
-        entry[i] = s.layer + 1; p0[i] = 0; nrow[i] = T;
-        break;
-      case TVR_SITE_ADD_ATTN_OUT_LASTPOS:
-        if (s.layer < 0 || s.layer >= L)
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": layer out of range");
-        if (!vectors || s.vec < 0 || s.vec >= n_vectors)
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": vector out of range");
-        entry[i] = s.layer + 1; p0[i] = T - 1; nrow[i] = 1;
-        break;
-      case TVR_SITE_SET_RESID_PRE_POS:
-        if (s.layer < 0 || s.layer >= L || s.pos < 0 || s.pos >= T || s.src_seq < 0 ||
-            s.src_seq >= trace->n_seq || s.src_pos < 0 || s.src_pos >= trace->seq_len[s.src_seq])
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": resid patch out of range");
-        entry[i] = s.layer; p0[i] = s.pos; nrow[i] = T - s.pos;
-        break;
-      case TVR_SITE_SET_RESID_PRE_VEC:  // planned as SET_RESID_PRE_POS; the row comes from `vectors`
-        if (s.layer < 0 || s.layer >= L || s.pos < 0 || s.pos >= T)
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": resid patch out of range");
-        if (!vectors || s.vec < 0 || s.vec >= n_vectors)
-          return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": vector out of range");
-        entry[i] = s.layer; p0[i] = s.pos; nrow[i] = T - s.pos;
-        break;
-      default:
-        return fail(TVR_ERR_INVALID, "site " + std::to_string(i) + ": unknown kind");
-    }
-  }
-  // every site computes one row (its last position: ADD_ATTN_OUT_LASTPOS,
-  // NONE, a SET_RESID_PRE_POS / SET_RESID_PRE_VEC of the last position): the site sequences go to
-  // the single-query attention kernel
-  bool single_rows = true;
-  for (int i = 0; i < n_sites; ++i) single_rows = single_rows && nrow[i] == 1;
-  // Shared prefixes (REPLACE_HEAD_ALLPOS): sites with the same (layer, head,
-  // vector) whose sequences start with the same tokens compute identical rows
-  // over that common prefix (position j attends to positions <= j only, and
-  // the patch is the same at every position).  The first such site (the
-  // leader) computes them; a follower starts at its common-prefix length P
-  // and reads positions < P's K/V from the leader's rows of this run
-  // (SeqDesc.prefix_live).  A CIE sweep's prompts all start with BOS, so
-  // (n_prompts - 1) / n_prompts of the position-0 rows — 1/T of the sweep's
-  // rows — are not recomputed.  The reference's batch-1 forwards compute that
-  // row identically for every prompt (scratch2.py:181-194).
-  std::vector<int> leader(n_sites, -1);
-  if (prefix_share_enabled() && (int)trace->tokens.size() >= trace->n_tokens) {
-    std::map<std::tuple<int, int, int, int>, int> first;
-    for (int i = 0; i < n_sites; ++i) {
-      const tvr_site& s = sites[i];
-      if (s.kind != TVR_SITE_REPLACE_HEAD_ALLPOS) continue;
-      const int32_t* tk = trace->tokens.data() + trace->seq_off[s.seq];
-      const auto key = std::make_tuple(s.layer, s.head, s.vec, (int)tk[0]);
-      const auto it = first.find(key);
-      if (it == first.end()) {
-        first.emplace(key, i);
-        continue;
-      }
-      const int ld = it->second;
-      const int32_t* tl = trace->tokens.data() + trace->seq_off[sites[ld].seq];
-      const int T = trace->seq_len[s.seq];
-      const int cap = std::min(T - 1, trace->seq_len[sites[ld].seq]);  // the last row stays the site's own
-      int P = 0;
-      while (P < cap && tk[P] == tl[P]) ++P;
-      if (P == 0) continue;
-      leader[i] = ld;
-      p0[i] = P;
-      nrow[i] = T - P;
-    }
-  }
-  std::vector<int> order(n_sites);
-  for (int i = 0; i < n_sites; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return entry[a] < entry[b]; });
-  std::vector<int> row0(n_sites);
-  std::vector<int> cnt_le(L + 1, 0), rows_le(L + 1, 0);  // sites / rows with entry <= l
-  int R = 0;
-  for (int k = 0; k < n_sites; ++k) {
-    const int i = order[k];
-    row0[i] = R;
-    R += nrow[i];
-  }
-  {
-    int k = 0, rows = 0;
-    for (int l = 0; l <= L; ++l) {
-      while (k < n_sites && entry[order[k]] <= l) { rows += nrow[order[k]]; ++k; }
-      cnt_le[l] = k;
-      rows_le[l] = rows;
-    }
-  }
-  // sequence descriptors: the fused clean sequences first, then the sites in entry order
-  std::vector<SeqDesc> seqs(nc + n_sites);
-  for (int s = 0; s < nc; ++s) seqs[s] = SeqDesc{trace->seq_off[s], trace->seq_len[s], 0, -1, 0, 0};
-  std::vector<EntryDesc> ents(n_sites);
-  for (int k = 0; k < n_sites; ++k) {
-    const int i = order[k];
-    const tvr_site& s = sites[i];
-    const int srow = trace->seq_off[s.seq];
-    seqs[nc + k] = leader[i] >= 0 ? SeqDesc{Rc + row0[i], nrow[i], p0[i], Rc + row0[leader[i]], 0, 1}
-                                  : SeqDesc{Rc + row0[i], nrow[i], p0[i], srow, 0, 0};
-    EntryDesc e{};
-    // a head-set site enters as a plain copy of its clean rows (the entry kernel's TVR_SITE_NONE path)
-    const bool set_kind = s.kind == TVR_SITE_REPLACE_HEADSET_ALLPOS || s.kind == TVR_SITE_REPLACE_HEADSET_LASTPOS;
-    e.kind = set_kind ? (int32_t)TVR_SITE_NONE : s.kind;
-    e.row0 = Rc + row0[i];
-    e.n = nrow[i];
-    e.p0 = p0[i];
-    e.src_row = srow;
-    e.src2_row = (s.kind == TVR_SITE_SET_RESID_PRE_POS) ? trace->seq_off[s.src_seq] + s.src_pos : 0;
-    e.patch_pos = s.pos;
-    e.head = s.head;
-    e.vec = s.vec;
-    ents[k] = e;
-  }
-  // entry layers' head-replacement sites grouped by head, at most ENTRY_GROUP per
-  // group, groups of one head balanced (entry_mfma.hpp); ent_other: the layer has sites of other kinds (entry_kernel)
-  std::vector<char> ent_other(L + 1, 0);
-  std::vector<int32_t> egidx;
-  std::vector<int2> egroups;
-  std::vector<int> eg_beg(L + 1, 0), eg_cnt(L + 1, 0);
-  for (int l = 0; l <= L; ++l) {
-    eg_beg[l] = (int)egroups.size();
-    std::map<int, std::vector<int>> byhead;
-    for (int k = l > 0 ? cnt_le[l - 1] : 0; k < cnt_le[l]; ++k) {
-      if (ents[k].kind == TVR_SITE_REPLACE_HEAD_ALLPOS)
-        byhead[ents[k].head].push_back(k);
-      else
-        ent_other[l] = 1;
-    }
-    for (const auto& hv : byhead) {  // ceil(n / ENTRY_GROUP) groups of balanced size (the launch ends with its
-      const size_t n = hv.second.size(), ng = (n + ENTRY_GROUP - 1) / ENTRY_GROUP;  // largest group)
-      for (size_t gi = 0; gi < ng; ++gi) {
-        const size_t a = gi * n / ng, b = (gi + 1) * n / ng;
-        egroups.push_back(make_int2((int)egidx.size(), (int)(b - a)));
-        egidx.insert(egidx.end(), hv.second.begin() + a, hv.second.begin() + b);
-      }
-    }
-    eg_cnt[l] = (int)egroups.size() - eg_beg[l];
-  }
-  // algorithmic bytes of each layer's entry launch (profiling): the clean rows
-  // read and the patched rows written, the vector, and for REPLACE_HEAD the
-  // head's z rows plus its W_O slice once per distinct head
-  std::vector<double> entry_bytes(L + 1, 0.0);  // entry layers 0..L (L: the final norm's input)
-  for (int l = 0; l <= L; ++l) {
-    std::vector<char> seen(c.n_heads, 0);
-    for (int k = l > 0 ? cnt_le[l - 1] : 0; k < cnt_le[l]; ++k) {
-      const EntryDesc& e = ents[k];
-      double b = (2.0 * e.n * d + d) * 4.0;
-      if (e.kind == TVR_SITE_REPLACE_HEAD_ALLPOS) {
-        b += (double)e.n * c.d_head * 4.0;
-        if (!seen[e.head]) b += (double)d * c.d_head * 4.0;
-        seen[e.head] = 1;
-      }
-      entry_bytes[l] += b;
-    }
-  }
-  std::vector<int32_t> last(n_sites), tg(n_sites);
-  for (int i = 0; i < n_sites; ++i) {
-    last[i] = Rc + row0[i] + nrow[i] - 1;
-    tg[i] = sites[i].target;
-  }
-  // the last layer computes every clean row (the trace keeps them) and each site's last row
-  std::vector<SeqDesc> seqs_last(seqs);
-  std::vector<int32_t> last_sorted(Rc + n_sites);
-  for (int r = 0; r < Rc; ++r) last_sorted[r] = r;
-  for (int k = 0; k < n_sites; ++k) {
-    seqs_last[nc + k].q0 = seqs_last[nc + k].n - 1;
-    last_sorted[Rc + k] = last[order[k]];
-  }
-  std::vector<int32_t> clean_last(nc), clean_tg(nc, -1);
-  for (int s = 0; s < nc; ++s) clean_last[s] = trace->seq_off[s] + trace->seq_len[s] - 1;
-  if (fused && !trace->p_targets.empty()) clean_tg = trace->p_targets;
-  const int ktop = std::max(topk, fused ? trace->p_k : 0);
-
-  // Head-set tables (headset_patch.hpp): per layer, one item per site with heads there (entry order) and
-  // the items' (head, vector) lists, each in the caller's order.
-  std::vector<HeadsetItem> hs_items;
-  std::vector<HeadsetPatch> hs_patches;
-  std::vector<int> hs_beg(L + 1, 0), hs_max_rows(L, 0);
-  std::vector<double> hs_bytes(L, 0.0);
-  if (set_off && set_off[n_sites] > set_off[0]) {
-    const double slice = (double)c.d_head * (act_fmt(m) == ACT_F32 ? 4.0 : act_fmt(m) == ACT_X2F16 ? 4.0 : 2.0);
-    std::vector<std::vector<std::pair<int, int>>> by_layer(L);  // (site, patch) in (entry order, list order)
-    for (int k = 0; k < n_sites; ++k)
-      for (int q = set_off[order[k]]; q < set_off[order[k] + 1]; ++q) by_layer[patches[q].layer].emplace_back(order[k], q);
-    for (int l = 0; l < L; ++l) {
-      hs_beg[l] = (int)hs_items.size();
-      const auto& bl = by_layer[l];
-      for (size_t x = 0; x < bl.size();) {
-        const int i = bl[x].first, first = (int)hs_patches.size();
-        for (; x < bl.size() && bl[x].first == i; ++x)
-          hs_patches.push_back(HeadsetPatch{patches[bl[x].second].head, patches[bl[x].second].vec});
-        const int np = (int)hs_patches.size() - first;
-        hs_items.push_back(HeadsetItem{Rc + row0[i], nrow[i], first, np});
-        hs_max_rows[l] = std::max(hs_max_rows[l], nrow[i]);
-        // slices zeroed + residual rows read and written + vectors read
-        hs_bytes[l] += (double)nrow[i] * (8.0 * d + slice * np) + 4.0 * d * np;
-      }
-    }
-    hs_beg[L] = (int)hs_items.size();
-  }
-
-  // Linearised entry layers (lin_entry.hpp): layer l in [1, L-2] of a fused
-  // sweep whose entering sites are all REPLACE_HEAD computes its entering
-  // rows' QKV + MLP-in outputs from the clean rows' (this sweep's rows
-  // [0, Rc)) and a K = d_head GEMM.  Tables per such layer: the distinct
-  // vectors (rows of G), the entering rows grouped by head, m-blocks of <= 64
-  // rows of one head.
-  const int fmt0 = act_fmt(m);
-  std::vector<char> use_lin(L, 0);
-  std::vector<int32_t> lin_vids;
-  std::vector<LinRow> lin_rows;
-  std::vector<LinMB> lin_mbs;
-  std::vector<int> lin_vid_off(L, 0), lin_nv(L, 0), lin_mb_off(L, 0), lin_nmb(L, 0), lin_nrows(L, 0);
-  int lin_max_nv = 0;
-  if (fused && fmt0 != ACT_F32 && L >= 3 && lin_entry_enabled()) {
-    for (int l = 1; l <= L - 2; ++l) {
-      const int k0 = cnt_le[l - 1], k1 = cnt_le[l];
-      bool ok = k1 > k0;
-      for (int k = k0; k < k1 && ok; ++k) ok = sites[order[k]].kind == TVR_SITE_REPLACE_HEAD_ALLPOS;
-      if (!ok) continue;
-      use_lin[l] = 1;
-      std::map<int, int> vrow;
-      lin_vid_off[l] = (int)lin_vids.size();
-      for (int k = k0; k < k1; ++k)
-        if (vrow.emplace(sites[order[k]].vec, (int)vrow.size()).second) lin_vids.push_back(sites[order[k]].vec);
-      lin_nv[l] = (int)vrow.size();
-      lin_max_nv = std::max(lin_max_nv, lin_nv[l]);
-      lin_mb_off[l] = (int)lin_mbs.size();
-      const int r_first = (int)lin_rows.size();
-      for (int h = 0; h < c.n_heads; ++h) {
-        const int g0 = (int)lin_rows.size();
-        for (int k = k0; k < k1; ++k) {
-          const int i = order[k];
-          const tvr_site& s = sites[i];
-          if (s.head != h) continue;
-          for (int q = 0; q < nrow[i]; ++q)
-            lin_rows.push_back(LinRow{Rc + row0[i] + q, trace->seq_off[s.seq] + p0[i] + q, vrow[s.vec], 0});
-        }
-        for (int r = g0; r < (int)lin_rows.size(); r += 64)
-          lin_mbs.push_back(LinMB{r, std::min(64, (int)lin_rows.size() - r), h, 0});
-      }
-      lin_nmb[l] = (int)lin_mbs.size() - lin_mb_off[l];
-      lin_nrows[l] = (int)lin_rows.size() - r_first;
-    }
-  }
-  bool any_lin = !lin_mbs.empty();
+  // --- plan (sweep_plan.hpp) ------------------------------------------------
+  const SweepPlanIn in{L, c.n_heads, d, c.d_head, trace->seq_off.data(), trace->seq_len.data(),
+                       trace->tokens.data(), trace->n_seq, trace->n_tokens, fused,
+                       prefix_share_enabled() && (int)trace->tokens.size() >= trace->n_tokens,
+                       fused && fmt != ACT_F32 && L >= 3 && lin_entry_enabled(), ENTRY_GROUP, n_vectors,
+                       vectors != nullptr, ((uintptr_t)vectors & 15) == 0, fmt == ACT_BF16 ? 2.0 : 4.0,
+                       sites, n_sites, set_off, patches};
+  SweepPlan p;
+  std::string err;
+  const int prc = plan_sweep(in, p, err);
+  if (prc != TVR_OK) return fail(prc, err);
+  const int Rc = p.Rc, nc = p.nc;
+  bool any_lin = !p.lin_mbs.empty();
   if (any_lin) {
     const int rc = ensure_lin(m, st);
     if (rc == TVR_ERR_NOMEM) {  // the W1 W_O planes do not fit: the full-GEMM entry (TVR_LIN_ENTRY=0) instead
       any_lin = false;
-      std::fill(use_lin.begin(), use_lin.end(), 0);
-      lin_vids.clear();
-      lin_rows.clear();
-      lin_mbs.clear();
-      lin_max_nv = 0;
+      p.drop_lin();
     } else {
       TVR_TRY(rc);
     }
   }
+  std::vector<int32_t> clean_tg(nc, -1);
+  if (fused && !trace->p_targets.empty()) clean_tg = trace->p_targets;
+  const int ktop = std::max(topk, fused ? trace->p_k : 0);
 
-  const int RA = Rc + R;  // rows of the activation buffers
+  // --- workspace and tables ---------------------------------------------------
+  const int RA = Rc + p.R;  // rows of the activation buffers
   // run_final chunks: the sites' (logits requested or not) and the fused clean rows' (never logits)
-  const int FCs = std::min(final_chunk(m, fmt0, out_logits), n_sites), FCc = std::min(final_chunk(m, fmt0, nullptr), nc);
+  const int FCs = std::min(final_chunk(m, fmt, out_logits), n_sites), FCc = std::min(final_chunk(m, fmt, nullptr), nc);
   Carve cv;
-  const size_t o_seqs = cv.take<SeqDesc>(nc + n_sites);
-  const size_t o_seqs_last = cv.take<SeqDesc>(nc + n_sites);
-  const size_t o_last_sorted = cv.take<int32_t>(Rc + n_sites);
-  const size_t o_ents = cv.take<EntryDesc>(n_sites);
-  const size_t o_last = cv.take<int32_t>(n_sites);
-  const size_t o_tg = cv.take<int32_t>(n_sites);
-  const size_t o_clast = cv.take<int32_t>(nc);
-  const size_t o_ctg = cv.take<int32_t>(nc);
-  const size_t o_ctok = cv.take<int32_t>(Rc);
-  // (uploaded tables first: flush_uploads sends one span from the first to the last)
-  const size_t o_lin_rows = cv.take<LinRow>(lin_rows.size());
-  const size_t o_lin_mbs = cv.take<LinMB>(lin_mbs.size());
-  const size_t o_lin_vids = cv.take<int32_t>(lin_vids.size());
-  const size_t o_egidx = cv.take<int32_t>(egidx.size());
-  const size_t o_egroups = cv.take<int2>(egroups.size());
-  const size_t o_hs_items = cv.take<HeadsetItem>(hs_items.size());  // (empty without set sites: no bytes)
-  const size_t o_hs_patches = cv.take<HeadsetPatch>(hs_patches.size());
+  UploadBatch ub;
+  // the uploaded tables first, carved in this order: flush_uploads sends one span from the first to the last
+  // (the clean tables are empty unless fused, the lin tables without lin layers, the head-set tables without sets)
+  auto table = [&](const auto& v) {
+    const size_t at = cv.take<typename std::decay_t<decltype(v)>::value_type>(v.size());
+    ub.add(at, v);
+    return at;
+  };
+  const size_t o_seqs = table(p.seqs);
+  const size_t o_seqs_last = table(p.seqs_last);
+  const size_t o_last_sorted = table(p.last_sorted);
+  const size_t o_ents = table(p.ents);
+  const size_t o_last = table(p.last);
+  const size_t o_tg = table(p.tg);
+  const size_t o_clast = table(p.clean_last);
+  const size_t o_ctg = table(clean_tg);
+  const size_t o_ctok = table(std::vector<int32_t>(trace->tokens.begin(), trace->tokens.begin() + Rc));
+  const size_t o_lin_rows = table(p.lin_rows);
+  const size_t o_lin_mbs = table(p.lin_mbs);
+  const size_t o_lin_vids = table(p.lin_vids);
+  const size_t o_egidx = table(p.egidx);
+  const size_t o_egroups = table(p.egroups);
+  const size_t o_hs_items = table(p.hs_items);
+  const size_t o_hs_patches = table(p.hs_patches);
   const size_t o_resid = cv.take<float>((size_t)RA * d);
   const size_t o_xn = cv.take<float>((size_t)RA * d);
   const size_t o_xn2 = use_x16(m) ? cv.take<float>((size_t)RA * d) : 0;
   const size_t o_qkv = cv.take<float>((size_t)RA * 3 * d);
   const size_t o_a2 = cv.take<float>((size_t)RA * m->K2);
   const size_t o_xf = cv.take<float>((size_t)std::max(FCs, FCc) * d);
-  const size_t o_lg = cv.take<float>(std::max(final_scratch_floats(m, fmt0, FCs, ktop, out_logits),
-                                              final_scratch_floats(m, fmt0, FCc, ktop, nullptr)));
+  const size_t o_lg = cv.take<float>(std::max(final_scratch_floats(m, fmt, FCs, ktop, out_logits),
+                                              final_scratch_floats(m, fmt, FCc, ktop, nullptr)));
   const size_t o_lnstats = cv.take<float2>(any_lin ? RA : 0);
   const size_t o_raw = cv.take<float>(any_lin ? (size_t)Rc * c.d_mlp : 0);
-  const size_t o_vact = cv.take<float>(any_lin ? (size_t)n_vectors * d : 0);  // vectors in the activation format
-  const size_t o_g = cv.take<float>((size_t)lin_max_nv * m->D1);
-  // exact-fp16 weights: one layer's G rows (centred vectors x LN1 / LN2 gamma, activation format)
-  const bool lin_x16 = any_lin && use_x16(m);
-  const size_t o_vg = cv.take<float>(lin_x16 ? (size_t)2 * lin_max_nv * d : 0);
+  const size_t o_vact = cv.take<float>(any_lin ? (size_t)n_vectors * d : 0);
+  const size_t o_g = cv.take<float>((size_t)p.lin_max_nv * m->D1);
+  const size_t o_vg = cv.take<float>(any_lin && use_x16(m) ? (size_t)2 * p.lin_max_nv * d : 0);
   TVR_TRY(ensure_workspace(m, cv.off, st));
   char* base = m->ws;
-  UploadBatch ub;
-  ub.add(o_seqs, seqs);
-  ub.add(o_seqs_last, seqs_last);
-  ub.add(o_last_sorted, last_sorted);
-  ub.add(o_ents, ents);
-  ub.add(o_last, last);
-  ub.add(o_tg, tg);
-  if (fused) {
-    ub.add(o_clast, clean_last);
-    ub.add(o_ctg, clean_tg);
-    ub.add(o_ctok, std::vector<int32_t>(trace->tokens.begin(), trace->tokens.begin() + Rc));
-  }
-  if (any_lin) {
-    ub.add(o_lin_rows, lin_rows);
-    ub.add(o_lin_mbs, lin_mbs);
-    ub.add(o_lin_vids, lin_vids);
-  }
-  ub.add(o_egidx, egidx);
-  ub.add(o_egroups, egroups);
-  if (!hs_items.empty()) {
-    ub.add(o_hs_items, hs_items);
-    ub.add(o_hs_patches, hs_patches);
-  }
   TVR_TRY(flush_uploads(m, st, base, ub));
 
-  const int fmt = act_fmt(m);
+  // --- run --------------------------------------------------------------------
   Acts a{(float*)(base + o_resid), (float*)(base + o_xn), (float*)(base + o_qkv),
          (float*)(base + o_a2), acts_fmt(m)};
   if (use_x16(m)) a.xn2 = (float*)(base + o_xn2);
-  const SeqDesc* d_seqs = (const SeqDesc*)(base + o_seqs);
-  const EntryDesc* d_ents = (const EntryDesc*)(base + o_ents);
+  const SweepCtx cx{m, trace, p, fused, a, vectors, st, (const SeqDesc*)(base + o_seqs),
+                    (const EntryDesc*)(base + o_ents), (const int32_t*)(base + o_egidx),
+                    (const EntryGroup*)(base + o_egroups), (const LinRow*)(base + o_lin_rows),
+                    (const LinMB*)(base + o_lin_mbs), (const int32_t*)(base + o_lin_vids),
+                    (float2*)(base + o_lnstats), (float*)(base + o_raw), (uint16_t*)(base + o_vact),
+                    (float*)(base + o_g), (uint16_t*)(base + o_vg)};
   const size_t tstride = (size_t)trace->max_tokens * d;
-  const size_t rbytes = (size_t)Rc * d * sizeof(float);  // the clean rows of one [rows][d] buffer
   if (fused) {
     const size_t total = (size_t)Rc * (d / 4);
     hipLaunchKernelGGL(embed_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, st,
                        (const int32_t*)(base + o_ctok), m->w_embed, a.resid, Rc, d);
     TVR_HIP(hipGetLastError());
   }
-
-  auto enter = [&](int l) -> int {
-    const int k0 = l > 0 ? cnt_le[l - 1] : 0, k1 = cnt_le[l];
-    if (k1 <= k0) return TVR_OK;
-    // the clean rows' hook_resid_pre: the live rows [0, Rc) in a fused sweep (the trace's copy is written by
-    // this layer's LayerNorm, after the entry), else the trace
-    const float* snap = fused ? a.resid : trace->resid + (size_t)l * tstride;
-    const float* zsnap = l > 0 ? trace->z + (size_t)(l - 1) * tstride : nullptr;
-    const float* w2 = l > 0 ? m->layers[l - 1].w2 : nullptr;
-    const dim3 eg(k1 - k0, (d + ENTRY_THREADS - 1) / ENTRY_THREADS);
-    ProfSpan ps(m, st);
-    const bool mf = eg_cnt[l] > 0 && (c.d_head == 16 || c.d_head == 64 || c.d_head == 80 || c.d_head == 128);
-    if (mf) {
-      const dim3 gg(eg_cnt[l], (d + ENTRY_COLS - 1) / ENTRY_COLS);
-      const int32_t* gidx = (const int32_t*)(base + o_egidx);
-      const int2* grps = (const int2*)(base + o_egroups) + eg_beg[l];
-#define TVR_ENTRY_MF(DH)                                                                                   \
-  hipLaunchKernelGGL(entry_replace_mfma_kernel<DH>, gg, dim3(ENTRY_THREADS), 0, st, d_ents, gidx, grps, snap, \
-                     zsnap, w2, m->K2, vectors, a.resid, d)
-      switch (c.d_head) {
-        case 16: TVR_ENTRY_MF(16); break;
-        case 64: TVR_ENTRY_MF(64); break;
-        case 80: TVR_ENTRY_MF(80); break;
-        default: TVR_ENTRY_MF(128); break;
-      }
-#undef TVR_ENTRY_MF
-      TVR_HIP(hipGetLastError());
-    }
-    if (ent_other[l] || !mf) {
-      const size_t zbytes = mf ? 0 : (size_t)std::min(maxT, ENTRY_LDS_POS) * c.d_head * sizeof(float);
-      if (zbytes > 64 * 1024)
-        TVR_HIP(hipFuncSetAttribute((const void*)entry_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)zbytes));
-      hipLaunchKernelGGL(entry_kernel, eg, dim3(ENTRY_THREADS), zbytes, st, d_ents + k0, snap, zsnap, w2, m->K2,
-                         vectors, a.resid, d, c.d_head, mf ? 1 : 0);
-      TVR_HIP(hipGetLastError());
-    }
-    ps.done(TVR_HBM_ENTRY, entry_bytes[l]);
-    return TVR_OK;
-  };
-
-  float2* lnstats = (float2*)(base + o_lnstats);
-  float* raw_h = (float*)(base + o_raw);
-  uint16_t* vact = (uint16_t*)(base + o_vact);
   if (any_lin) {
     const size_t n = (size_t)n_vectors * d;
     const dim3 g((unsigned)std::min<size_t>((n + 255) / 256, 8192));
     if (fmt == ACT_X2F16)
-      hipLaunchKernelGGL(act_rows_kernel<ACT_X2F16>, g, dim3(256), 0, st, vectors, d, vact, n_vectors, d,
+      hipLaunchKernelGGL(act_rows_kernel<ACT_X2F16>, g, dim3(256), 0, st, vectors, d, cx.vact, n_vectors, d,
                          m->range_flag);
     else  // bf16 plane + the fp16 plane the Q / K columns of G read (as LayerNorm's store_ln4)
-      hipLaunchKernelGGL(act_rows_bf16_f16_kernel, g, dim3(256), 0, st, vectors, d, vact, n_vectors, d);
+      hipLaunchKernelGGL(act_rows_bf16_f16_kernel, g, dim3(256), 0, st, vectors, d, cx.vact, n_vectors, d);
     TVR_HIP(hipGetLastError());
   }
-  // layer l's block with the linearised entry rows [Rp, Rl) (use_lin[l])
-  auto run_block_lin = [&](int l, int Rl, const float* cache, float* zf) -> int {
-    const tvr_layer_weights& w = m->layers[l];
-    const int Rp = Rc + rows_le[l - 1], D1 = m->D1;
-    TVR_TRY(launch_lnpre(a.resid, d, nullptr, a.xn, d, Rl, d, c.ln_eps, a.fmt, st, m, lnstats, a.resid_mirror,
-                         a.mirror_rows, a.xn2 ? m->g1[l] : nullptr, a.xn2 ? m->g2[l] : nullptr, a.xn2));
-    GemmEpi e1 = epi_qkv_mlpin(m, w.b1, a.qkv, a);
-    e1.raw = raw_h;
-    e1.raw_rows = Rc;
-    e1.ld_raw = c.d_mlp;
-    TVR_TRY(launch_w1(m, l, a.xn, Rp, 0, D1, e1, st, a.xn2));
-    ProfSpan ps(m, st);
-    const bool prof = m->prof;
-    m->prof = false;  // G and the entry rows are timed as one HBM-kind span, not as GEMM-family launches
-    GemmEpi eg{};
-    eg.out0 = (float*)(base + o_g);
-    eg.ld0 = D1;
-    eg.a_rows = (const int32_t*)(base + o_lin_vids) + lin_vid_off[l];
-    eg.skinny = 1;
-    int rc = TVR_OK;
-    const int nqk = fmt == ACT_BF16 && !m->w1qk.empty() ? 2 * d : 0;  // bf16: Q / K columns on fp16 operands
-    if (lin_x16) {
-      // G = v W1'^T on the raw fp16 W1 (one plane, 2 products): rows ((v - mean) o gamma1 | gamma2), lin_entry.hpp
-      uint16_t* vg1 = (uint16_t*)(base + o_vg);
-      uint16_t* vg2 = vg1 + (size_t)2 * lin_nv[l] * d;
-      hipLaunchKernelGGL(lin_gamma_rows_kernel, dim3((lin_nv[l] + 3) / 4), dim3(256), 0, st, vectors, d,
-                         (const int32_t*)(base + o_lin_vids) + lin_vid_off[l], m->g1[l], m->g2[l], vg1, vg2,
-                         lin_nv[l], m->range_flag);
-      rc = hipGetLastError() == hipSuccess ? TVR_OK : fail(TVR_ERR_HIP, "lin_gamma_rows_kernel launch");
-      GemmEpi ex = eg;
-      ex.a_rows = nullptr;  // the rows are the layer's vectors in order
-      const int q = 3 * d;  // first MLP-in column: it and the columns after it read the gamma2 rows
-      if (rc == TVR_OK && q % 256 == 0) {
-        ex.a2 = vg2;
-        ex.a2_col = q;
-        rc = launch_gemm(EPI_BIAS, vg1, d, fmt, m->w1x[l], d, lin_nv[l], D1, d, ex, st, m);
-      } else if (rc == TVR_OK) {  // two launches (d % 256 != 0: the tiny test model)
-        rc = launch_gemm(EPI_BIAS, vg1, d, fmt, m->w1x[l], d, lin_nv[l], q, d, ex, st, m);
-        GemmEpi e2 = ex;
-        e2.out0 = ex.out0 + q;
-        if (rc == TVR_OK)
-          rc = launch_gemm(EPI_BIAS, vg2, d, fmt, m->w1x[l].rows((size_t)q * d), d, lin_nv[l], D1 - q, d, e2, st, m);
-      }
-    } else if (nqk > 0) {
-      rc = launch_gemm(EPI_BIAS, vact + d, d, ACT_F16, m->w1qk[l], d, lin_nv[l], nqk, d, eg, st, m);
-      GemmEpi e2 = eg;
-      e2.out0 = eg.out0 + nqk;
-      if (rc == TVR_OK)
-        rc = launch_gemm(EPI_BIAS, vact, d, fmt, m->w1[l].rows((size_t)nqk * d), d, lin_nv[l], D1 - nqk, d, e2, st,
-                         m);
-    } else {
-      rc = launch_gemm(EPI_BIAS, vact, d, fmt, m->w1[l], d, lin_nv[l], D1, d, eg, st, m);
-    }
-    m->prof = prof;
-    TVR_TRY(rc);
-    const int npl = fmt == ACT_X2F16 ? 2 : 1, KP = m->lin_kp;
-    const size_t per = (size_t)c.n_heads * D1 * KP;
-    const uint16_t* wp = m->lin_planes + (size_t)(l - 1) * npl * per;
-    // X2F16: every column tile in one launch; BF16: the Q / K column tiles [0, 2d) on the fp16 rows of the
-    // planes (scale lin_scale[l]), the rest on bf16
-    const int n_ct = (D1 + 255) / 256, ct_qk = fmt == ACT_BF16 ? lin_qk_cols(c) / 256 : 0;
-    float acc_scale = fmt == ACT_X2F16 ? 1.0f / (m->lin_scale[l] * X2_ASCALE) : 1.0f;
-    dim3 g;
-    int ct_base = 0;
-#define TVR_LIN(F, NK, ...)                                                                                        \
-  hipLaunchKernelGGL((lin_entry_kernel<F, NK __VA_OPT__(,) __VA_ARGS__>), g, dim3(LIN_THREADS), 0, st,              \
-                     (const LinMB*)(base + o_lin_mbs) + lin_mb_off[l], lin_nmb[l], (const LinRow*)(base + o_lin_rows), \
-                     wp, per, acc_scale, trace->z + (size_t)(l - 1) * tstride, d, c.d_head, lnstats, a.qkv, raw_h,     \
-                     c.d_mlp, (const float*)(base + o_g), m->lin_c1 + (size_t)l * D1, w.b1, D1,                         \
-                     reinterpret_cast<uint16_t*>(a.a2) + act_col_rt(a.fmt, d), 2 * m->K2, m->K2, m->range_flag, ct_base)
-#define TVR_LIN_K(F, ...)                                                 \
-  if (KP == 32) TVR_LIN(F, 1 __VA_OPT__(,) __VA_ARGS__);                  \
-  else if (KP == 64) TVR_LIN(F, 2 __VA_OPT__(,) __VA_ARGS__);             \
-  else if (KP == 96) TVR_LIN(F, 3 __VA_OPT__(,) __VA_ARGS__);             \
-  else TVR_LIN(F, 4 __VA_OPT__(,) __VA_ARGS__)
-    if (fmt == ACT_X2F16 && a.fmt == ACT_X2F16I) {  // a2's GELU planes interleaved
-      g = dim3(lin_nmb[l] * n_ct);
-      TVR_LIN_K(ACT_X2F16, true);
-    } else if (fmt == ACT_X2F16) {
-      g = dim3(lin_nmb[l] * n_ct);
-      TVR_LIN_K(ACT_X2F16);
-    } else {
-      if (ct_qk > 0) {
-        g = dim3(lin_nmb[l] * ct_qk);
-        acc_scale = 1.0f / m->lin_scale[l];
-        TVR_LIN_K(ACT_F16);
-      }
-      g = dim3(lin_nmb[l] * (n_ct - ct_qk));
-      acc_scale = 1.0f;
-      ct_base = ct_qk;
-      TVR_LIN_K(ACT_BF16);
-    }
-#undef TVR_LIN_K
-#undef TVR_LIN
-    TVR_HIP(hipGetLastError());
-    // algorithmic bytes: the entering rows' outputs written and their clean rows' y_c read (4 B per
-    // column each), z slices, the layer's Wsc planes once, G written + read, the vectors' planes
-    const double nr = lin_nrows[l];
-    ps.done(TVR_HBM_LIN_ENTRY, nr * (8.0 * D1 + 4.0 * c.d_head) + 2.0 * npl * per +
-                                   lin_nv[l] * (8.0 * D1 + 4.0 * d) + 2.0 * npl * (double)D1 * d);
-    ProfSpan pa(m, st);
-    TVR_TRY(launch_attention(m, a.qkv, cache, d_seqs, nc + cnt_le[l], maxT, a.a2, a.fmt, zf, st, false, Rc));
-    pa.done(TVR_HBM_ATTENTION, attention_bytes(d, Rl, Rl, a.fmt, zf ? std::min(Rl, Rc) : 0));
-    return run_block_out(m, l, Rl, a, st);
-  };
-
   for (int l = 0; l < L; ++l) {
-    const int Rl = Rc + rows_le[l];
+    const int Rl = Rc + p.rows_le[l];
     float* tqkv = trace->qkv + (size_t)l * 3 * tstride;
     if (fused) {  // the clean rows' hook_resid_pre / K,V cache go to the trace from the kernels writing them
       a.resid_mirror = trace->resid + l * tstride;
       a.qkv_mirror = tqkv;
       a.mirror_rows = Rc;
     }
-    TVR_TRY(enter(l));
+    TVR_TRY(sweep_enter(cx, l));
     if (Rl == 0) continue;
-    a.hs_n = hs_beg[l + 1] - hs_beg[l];  // this layer's head-set patches (0 without set sites)
+    a.hs_n = p.hs_beg[l + 1] - p.hs_beg[l];  // this layer's head-set patches (0 without set sites)
     if (a.hs_n > 0) {
-      a.hs_items = (const HeadsetItem*)(base + o_hs_items) + hs_beg[l];
+      a.hs_items = (const HeadsetItem*)(base + o_hs_items) + p.hs_beg[l];
       a.hs_patches = (const HeadsetPatch*)(base + o_hs_patches);
       a.hs_vectors = vectors;
-      a.hs_max_rows = hs_max_rows[l];
-      a.hs_bytes = hs_bytes[l];
+      a.hs_max_rows = p.hs_max_rows[l];
+      a.hs_bytes = p.hs_bytes[l];
     }
     const float* cache = fused ? a.qkv : tqkv;
     float* zf = fused ? trace->z + l * tstride : nullptr;  // the clean rows' hook_z (rows < Rc)
-    if (use_lin[l]) {
-      TVR_TRY(run_block_lin(l, Rl, cache, zf));
-    } else if (l == L - 1 && Rc + cnt_le[l] < Rl) {  // (every row a last row, e.g. C2's: the plain block)
-      TVR_TRY(run_block_last_rows(m, l, Rl, (const SeqDesc*)(base + o_seqs_last), nc + cnt_le[l], maxT, a, cache,
-                                  (const int32_t*)(base + o_last_sorted), Rc + cnt_le[l], true, zf, st, false, Rc,
+    if (p.use_lin[l]) {
+      TVR_TRY(sweep_block_lin(cx, l, Rl, cache, zf));
+    } else if (l == L - 1 && Rc + p.cnt_le[l] < Rl) {  // (every row a last row, e.g. C2's: the plain block)
+      TVR_TRY(run_block_last_rows(m, l, Rl, (const SeqDesc*)(base + o_seqs_last), nc + p.cnt_le[l], p.maxT, a, cache,
+                                  (const int32_t*)(base + o_last_sorted), Rc + p.cnt_le[l], true, zf, st, false, Rc,
                                   nc));
     } else {
-      TVR_TRY(run_block(m, l, Rl, d_seqs, nc + cnt_le[l], maxT, a, a.qkv, cache, zf, st, false, Rc,
-                        single_rows ? nc : INT_MAX));
+      TVR_TRY(run_block(m, l, Rl, cx.seqs, nc + p.cnt_le[l], p.maxT, a, a.qkv, cache, zf, st, false, Rc,
+                        p.single_rows ? nc : INT_MAX));
       TVR_TRY(run_block_out(m, l, Rl, a, st));
     }
   }
   a.resid_mirror = a.qkv_mirror = nullptr;
   a.mirror_rows = 0;
   if (fused) {
-    TVR_HIP(hipMemcpyAsync(trace->resid + L * tstride, a.resid, rbytes, hipMemcpyDeviceToDevice, st));
+    TVR_HIP(hipMemcpyAsync(trace->resid + L * tstride, a.resid, (size_t)Rc * d * sizeof(float),
+                           hipMemcpyDeviceToDevice, st));
     trace->pending = false;
   }
-  TVR_TRY(enter(L));
+  TVR_TRY(sweep_enter(cx, L));
   TVR_TRY(run_final(m, a.resid, (const int32_t*)(base + o_last), (const int32_t*)(base + o_tg), n_sites,
                     (float*)(base + o_xf), (float*)(base + o_lg), out_prob, out_topk, topk, out_logits, fmt, st));
   if (fused && (trace->p_prob || trace->p_topk))

@@ -50,15 +50,15 @@ constexpr int ENTRY_COLS = (ENTRY_THREADS / 64) * 16 * ENTRY_NT;   // columns pe
 template <int DH>
 __global__ void __launch_bounds__(ENTRY_THREADS)
 entry_replace_mfma_kernel(const EntryDesc* __restrict__ ents, const int32_t* __restrict__ gidx,
-                          const int2* __restrict__ groups, const float* __restrict__ snap,
+                          const EntryGroup* __restrict__ groups, const float* __restrict__ snap,
                           const float* __restrict__ zsnap, const float* __restrict__ w2, int ldw2,
                           const float* __restrict__ vectors, float* __restrict__ resid, int d) {
   constexpr int CH = DH / 4;  // k values per lane group
   static_assert(DH % 16 == 0, "d_head");
   __shared__ __attribute__((aligned(16))) float zt[16 * (DH + 4)];  // 16 positions x DH (+4: conflict-free rows)
   constexpr int LDZ = DH + 4;
-  const int2 grp = groups[blockIdx.x];  // entries gidx[grp.x .. + grp.y): REPLACE_HEAD sites of one head
-  const int head = ents[gidx[grp.x]].head;
+  const EntryGroup grp = groups[blockIdx.x];  // entries gidx[first .. + count): REPLACE_HEAD sites of one head
+  const int head = ents[gidx[grp.first]].head;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int li = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.y * ENTRY_COLS + wave * 16 * ENTRY_NT;  // this wave's first column
@@ -75,8 +75,8 @@ entry_replace_mfma_kernel(const EntryDesc* __restrict__ ents, const int32_t* __r
       wb[nt][q] = v4.x; wb[nt][q + 1] = v4.y; wb[nt][q + 2] = v4.z; wb[nt][q + 3] = v4.w;
     }
   }
-  for (int gi = 0; gi < grp.y; ++gi) {
-    const EntryDesc e = ents[gidx[grp.x + gi]];
+  for (int gi = 0; gi < grp.count; ++gi) {
+    const EntryDesc e = ents[gidx[grp.first + gi]];
     for (int t0 = 0; t0 < e.n; t0 += 16) {
       const int tn = min(16, e.n - t0);
       __syncthreads();  // the previous tile's reads are done

@@ -28,18 +28,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace tvr {
+#include "sweep_desc.hpp"  // HeadsetItem, HeadsetPatch
 
-struct HeadsetItem {
-  int32_t row0;         // first row of the site in the activation buffers
-  int32_t n_rows;       // the site's rows (all positions: T, last position: 1)
-  int32_t first_patch;  // range of the flat patch list: the site's heads at this layer
-  int32_t n_patches;
-};
-struct HeadsetPatch {
-  int32_t head;
-  int32_t vec;  // row of `vectors`
-};
+namespace tvr {
 
 constexpr int HEADSET_THREADS = 256;
 constexpr int HEADSET_ROWS = 8;  // rows per block: their residual loads precede their stores

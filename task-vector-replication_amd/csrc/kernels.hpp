@@ -11,38 +11,11 @@
 #include <stdint.h>
 
 #include "split.hpp"
+#include "sweep_desc.hpp"
 
 namespace tvr {
 
-// ---------------------------------------------------------------------------
-// Descriptors built by the host planner (engine.hip).
-
-// One sequence as seen by attention at a layer: its computed rows are the
-// positions [p0, p0+n); positions [0, p0) come from the clean trace's K/V.
-struct SeqDesc {
-  int32_t row0;       // first computed row in the activation buffers
-  int32_t n;          // number of computed rows
-  int32_t p0;         // absolute position of row0
-  int32_t cache_row;  // row of position 0 for the K/V prefix (positions < p0), -1: none
-  int32_t q0;         // first computed row that is a query (n-1: last row only)
-  int32_t prefix_live;  // 0: the prefix is in the clean trace (cache); 1: in this run's qkv rows
-                        // (a shared-prefix follower reads its leader's rows: tvr_patch_sweep)
-};
-
-// How a patch site's residual is materialised at its entry layer e
-// (resid_pre[e] rows [p0, p0+n)), from the clean trace.
-struct EntryDesc {
-  int32_t kind;       // tvr_site_kind
-  int32_t row0;       // destination row (activation buffer)
-  int32_t n;          // rows
-  int32_t p0;         // first position
-  int32_t src_row;    // trace row of position 0 of `seq`
-  int32_t src2_row;   // SET_RESID_PRE_POS: trace row supplying the patched position
-  int32_t patch_pos;  // SET_RESID_PRE_POS / _VEC: absolute patched position
-  int32_t head;       // REPLACE_HEAD
-  int32_t vec;        // vector row (SET_RESID_PRE_VEC: the row written at patch_pos)
-  int32_t pad;
-};
+// Descriptors built by the host planner (sweep_plan.hpp): SeqDesc, EntryDesc in sweep_desc.hpp.
 
 // ---------------------------------------------------------------------------
 // wave_sum / wave_max: split.hpp

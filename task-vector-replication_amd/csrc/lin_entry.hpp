@@ -23,19 +23,9 @@
 #include <stdint.h>
 
 #include "gemm_planar.hpp"
+#include "sweep_desc.hpp"  // LinMB, LinRow
 
 namespace tvr {
-
-// One block's rows: entering rows [row0, row0 + rows) of the layer's row list
-// (rows <= 64), all of head `head`.
-struct LinMB {
-  int row0, rows, head, pad;
-};
-// One entering row: its activation row, its clean row (trace row of the same
-// prompt position: y_c, z_h and the clean LN statistics) and its vector's row of G.
-struct LinRow {
-  int out_row, clean_row, vrow, pad;
-};
 
 constexpr int LIN_THREADS = 256;  // 4 waves, each 64 rows x 64 columns of a 64 x 256 tile
 
