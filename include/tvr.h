@@ -408,6 +408,43 @@ int tvr_gemm_planar(int32_t fmt, const uint16_t* A, int32_t lda, const uint16_t*
 /* TransformerLens LayerNormPre over rows: (x - mean) / sqrt(var + eps) */
 int tvr_lnpre_f32(const float* x, int32_t ldx, float* y, int32_t ldy,
                   int32_t rows, int32_t d, float eps, void* stream);
+/* The engine's causal attention of ragged sequences, launched exactly as a
+ * block of the model launches it (the kernel form is chosen from the longest
+ * p0 + n, TVR_ATT_STAGE / TVR_ATT_VSTAGE / TVR_ROW_ATTN and row_from).
+ * A sequence computes the rows [row0, row0 + n) of qkv, the positions
+ * [p0, p0 + n); the K / V rows of positions [0, p0) are rows cache_row .. of
+ * `cache` (prefix_live 0) or of qkv itself (prefix_live 1: a leader's rows of
+ * the same launch); rows [q0, n) are queries.  Sequences [row_from, n_seq)
+ * have exactly one query (q0 = n - 1) and take the single-query kernel where
+ * the model's n_heads allows it; row_from = n_seq: none.
+ *   qkv    device [rows][3 d]: Q | K | V per row, before rotary
+ *   cache  device [cache_rows][3 d] (its Q columns are not read), or NULL
+ *   seqs   host [n_seq]
+ *   fmt    0: z is fp32 [rows][K2], K2 = d_model + d_mlp; TVR_GEMM_X2F16,
+ *          TVR_ACT_X2F16_IL, TVR_GEMM_BF16: z is halves [rows][2 K2] in the
+ *          format tvr_act_rows describes (the layout of the engine's buffer
+ *          for the O + MLP-out GEMM's input).  Only columns [0, d) of the
+ *          query rows are written.
+ *   zf     device fp32 [.][d] or NULL: a copy of z's query rows with row
+ *          index < zf_rows (zf_last 0), or of sequence s' last row at row s
+ *          (zf_last 1)
+ *   cos_t, sin_t  device [n_ctx][d_head / 4] rotary tables (TransformerLens'
+ *          calculate_sin_cos_rotary layout), or both NULL: the model's own
+ * All arguments are validated on the host before any device call:
+ * TVR_ERR_INVALID for a null model / qkv / z / seqs, n_seq <= 0, an unknown
+ * fmt, a buffer that is not 16-byte aligned, one table without the other,
+ * row_from outside [0, n_seq], rows <= 0, cache_rows < 0, zf_rows < 0, and
+ * per sequence n < 1, q0 outside [0, n),
+ * p0 < 0, p0 + n > n_ctx, rows outside [0, rows), with p0 > 0 a negative
+ * cache_row, a prefix outside its buffer or a null cache, and q0 != n - 1 at or
+ * after row_from.  A test primitive: it copies the descriptors to a temporary
+ * device buffer and synchronises `stream`.  An x2f16 value with |z| >= 4095
+ * is reported by tvr_model_range_status.  (Backward-compatible addition: ABI 11.) */
+typedef struct tvr_attn_seq { int32_t row0, n, p0, cache_row, q0, prefix_live; } tvr_attn_seq;
+int tvr_attention(tvr_model* model, int32_t fmt, const float* qkv, const float* cache,
+                  const tvr_attn_seq* seqs, int32_t n_seq, int32_t row_from, int32_t rows,
+                  int32_t cache_rows, void* z, float* zf, int32_t zf_last, int32_t zf_rows,
+                  const float* cos_t, const float* sin_t, void* stream);
 
 /* Kernel timing (HIP events recorded on the launch stream around every GEMM
  * launch while enabled).  tvr_profile_read synchronises the recorded events

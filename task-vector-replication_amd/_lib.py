@@ -66,6 +66,15 @@ class CHeadPatch(ctypes.Structure):
     _fields_ = [("layer", ctypes.c_int32), ("head", ctypes.c_int32), ("vec", ctypes.c_int32)]
 
 
+class CAttnSeq(ctypes.Structure):
+    """Mirror of ``tvr_attn_seq`` (include/tvr.h; the kernels' SeqDesc)."""
+    _fields_ = [("row0", ctypes.c_int32), ("n", ctypes.c_int32), ("p0", ctypes.c_int32),
+                ("cache_row", ctypes.c_int32), ("q0", ctypes.c_int32), ("prefix_live", ctypes.c_int32)]
+
+
+ACT_X2F16_IL = 0x12  # include/tvr.h TVR_ACT_X2F16_IL
+
+
 class CKernelStats(ctypes.Structure):
     _fields_ = [("gemm_launches", ctypes.c_int64 * 3), ("gemm_flops", ctypes.c_double * 3),
                 ("gemm_ms", ctypes.c_double * 3), ("gemm_bytes", ctypes.c_double * 3)]
@@ -150,6 +159,9 @@ SIGNATURES = {
     "tvr_profile_read_hbm": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CHbmStats)]),
     "tvr_gemm_plan": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_void_p]),
+    "tvr_attention": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_int32,
+                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, c_f32p,
+                                     ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p]),
 }
 
 OPS_PATH = LIB_PATH.parent / OPS_NAME

@@ -527,7 +527,15 @@ attention_row_kernel(const float* __restrict__ qkv, int ldq, const float* __rest
 #pragma unroll
       for (int o = LPH / 2; o > 0; o >>= 1) sc += __shfl_xor(sc, o, 64);
       if (j >= T) continue;  // wave-uniform (T is the sequence's)
-      sc *= inv_attn_scale;
+      {
+        // the scaled score is rounded once and that number enters both the running max and the exponent.
+        // Left to contraction the product was fused into the subtraction below (fma(sc, scale, -m_new))
+        // while m_new held the rounded product: for 1 / sqrt(d_head) not a power of two (d_head 80, 128) the
+        // best key's weight was exp(the product's rounding error), not 1, and a one-hot pattern returned
+        // V's row 1 ulp off (tests/test_gpu_attention.py test_select_is_bitwise)
+#pragma clang fp contract(off)
+        sc = sc * inv_attn_scale;
+      }
       const float m_new = fmaxf(m_run, sc);
       const float scale = m_run == -INFINITY ? 0.f : expf(m_run - m_new);
       const float p = expf(sc - m_new);

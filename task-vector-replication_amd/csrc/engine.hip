@@ -1081,9 +1081,13 @@ bool row_attention_ok(const tvr_config& c) {
 
 int launch_attention(tvr_model* m, const float* qkv, const float* cache_qkv, const SeqDesc* d_seqs,
                      int n_seqs, int maxT, void* z, int fmt, float* zf, hipStream_t st, bool zf_last = false,
-                     int zf_rows = INT_MAX, int row_from = INT_MAX) {
+                     int zf_rows = INT_MAX, int row_from = INT_MAX, const float* cos_t = nullptr,
+                     const float* sin_t = nullptr) {
   if (n_seqs <= 0) return TVR_OK;
   const tvr_config& c = m->cfg;
+  // the rotary tables: the model's, or a caller's of the same layout (tvr_attention)
+  const float* rot_cos = cos_t ? cos_t : m->rot_cos;
+  const float* rot_sin = sin_t ? sin_t : m->rot_sin;
   const int d = c.d_model;
   const float inv_scale = 1.0f / std::sqrt((float)c.d_head);
   const int dh = c.d_head;
@@ -1092,7 +1096,7 @@ int launch_attention(tvr_model* m, const float* qkv, const float* cache_qkv, con
     const dim3 rg((nr * (c.n_heads / hg) + 3) / 4), rb(256);
 #define TVR_ATTR(F, DHV)                                                                                         \
   hipLaunchKernelGGL((attention_row_kernel<F, DHV>), rg, rb, 0, st, qkv, 3 * d, cache_qkv, 3 * d, d_seqs, row_from, \
-                     nr, c.n_heads, z, m->K2, zf, d, zf_last ? 1 : 0, zf_rows, m->range_flag, m->rot_cos, m->rot_sin, \
+                     nr, c.n_heads, z, m->K2, zf, d, zf_last ? 1 : 0, zf_rows, m->range_flag, rot_cos, rot_sin, \
                      d, inv_scale)
 #define TVR_ATTR_DH(F)                                                                         \
   if (dh == 16) { TVR_ATTR(F, 16); } else if (dh == 64) { TVR_ATTR(F, 64); }                   \
@@ -1124,7 +1128,7 @@ int launch_attention(tvr_model* m, const float* qkv, const float* cache_qkv, con
   const bool vstage = env_flag("TVR_ATT_VSTAGE");  // read per launch, as TVR_ATT_STAGE (in-process A/B tests)
 #define TVR_ATTM(F, DHV, NK, ...)                                                                                   \
   hipLaunchKernelGGL((attention_mfma_kernel<F, DHV, NK __VA_OPT__(,) __VA_ARGS__>), grid, block, 0, st, qkv, 3 * d, cache_qkv, 3 * d, d_seqs, \
-                     n_seqs, c.n_heads, z, m->K2, zf, d, zf_last ? 1 : 0, zf_rows, m->range_flag, m->rot_cos, m->rot_sin, d, \
+                     n_seqs, c.n_heads, z, m->K2, zf, d, zf_last ? 1 : 0, zf_rows, m->range_flag, rot_cos, rot_sin, d, \
                      inv_scale)
 #define TVR_ATTM_NK(F, DHV)                                                                     \
   if (nkt == 1 && stage == 1) TVR_ATTM(F, DHV, 1, (DHV <= 80 ? 1 : 0)); /* d_head 128: 98 KB, not staged */ \
@@ -2701,6 +2705,65 @@ int tvr_lnpre_f32(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t ro
                   void* stream) {
   if (!x || !y || rows < 0 || d <= 0) return fail(TVR_ERR_INVALID, "tvr_lnpre_f32: bad argument");
   return launch_lnpre(x, ldx, nullptr, y, ldy, rows, d, eps, ACT_F32, (hipStream_t)stream);
+}
+
+static_assert(sizeof(tvr_attn_seq) == sizeof(SeqDesc), "tvr_attn_seq is SeqDesc");
+
+int tvr_attention(tvr_model* m, int32_t fmt, const float* qkv, const float* cache, const tvr_attn_seq* seqs,
+                  int32_t n_seq, int32_t row_from, int32_t rows, int32_t cache_rows, void* z, float* zf,
+                  int32_t zf_last, int32_t zf_rows, const float* cos_t, const float* sin_t, void* stream) {
+  // every check on the host, before any device call: a wrong descriptor never becomes a device read
+  auto bad = [](const std::string& what) { return fail(TVR_ERR_INVALID, "tvr_attention: " + what); };
+  if (!m) return bad("null model");
+  if (!qkv) return bad("null qkv");
+  if (!z) return bad("null z");
+  if (!seqs) return bad("null seqs");
+  if (n_seq <= 0) return bad("n_seq must be positive");
+  if (fmt != 0 && fmt != TVR_GEMM_X2F16 && fmt != TVR_ACT_X2F16_IL && fmt != TVR_GEMM_BF16)
+    return bad("unknown fmt " + std::to_string(fmt));
+  if (fmt == TVR_ACT_X2F16_IL && m->K2 % 32 != 0) return bad("the interleaved format needs K2 % 32 == 0");
+  if (rows <= 0 || cache_rows < 0) return bad("rows must be positive and cache_rows non-negative");
+  if (zf_rows < 0) return bad("zf_rows is negative");  // the kernels compare it as size_t
+  if (row_from < 0 || row_from > n_seq) return bad("row_from outside [0, n_seq]");
+  if ((cos_t == nullptr) != (sin_t == nullptr)) return bad("cos_t and sin_t must both be given or both be null");
+  if (((uintptr_t)qkv | (uintptr_t)cache | (uintptr_t)z | (uintptr_t)zf) & 15)
+    return bad("qkv, cache, z and zf must be 16-byte aligned");
+  const int n_ctx = m->cfg.n_ctx;
+  int maxT = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    const tvr_attn_seq& q = seqs[s];
+    const std::string at = " (sequence " + std::to_string(s) + ")";
+    if (q.n < 1) return bad("n must be at least 1" + at);
+    if (q.q0 < 0 || q.q0 >= q.n) return bad("q0 outside [0, n)" + at);
+    if (q.p0 < 0) return bad("p0 is negative" + at);
+    if ((int64_t)q.p0 + q.n > n_ctx) return bad("p0 + n exceeds n_ctx" + at);
+    if (q.row0 < 0 || (int64_t)q.row0 + q.n > rows) return bad("rows [row0, row0 + n) outside the qkv buffer" + at);
+    if (q.prefix_live != 0 && q.prefix_live != 1) return bad("prefix_live must be 0 or 1" + at);
+    if (q.p0 > 0) {
+      if (q.cache_row < 0) return bad("cache_row is negative with p0 > 0" + at);
+      if (q.prefix_live == 0 && !cache) return bad("null cache with p0 > 0 and prefix_live 0" + at);
+      if ((int64_t)q.cache_row + q.p0 > (q.prefix_live ? rows : cache_rows))
+        return bad(std::string("prefix rows [cache_row, cache_row + p0) outside the ") +
+                   (q.prefix_live ? "qkv" : "cache") + " buffer" + at);
+    }
+    if (s >= row_from && q.q0 != q.n - 1) return bad("a sequence at or after row_from needs q0 == n - 1" + at);
+    maxT = std::max(maxT, q.p0 + q.n);
+  }
+  const int afmt = fmt == 0 ? ACT_F32 : fmt == TVR_GEMM_X2F16 ? ACT_X2F16 : fmt == TVR_ACT_X2F16_IL ? ACT_X2F16I : ACT_BF16;
+  const hipStream_t st = (hipStream_t)stream;
+  SeqDesc* d_seqs = nullptr;
+  if (hipMalloc(&d_seqs, (size_t)n_seq * sizeof(SeqDesc)) != hipSuccess)
+    return fail(TVR_ERR_NOMEM, "tvr_attention: descriptor buffer");
+  hipError_t e = hipMemcpyAsync(d_seqs, seqs, (size_t)n_seq * sizeof(SeqDesc), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // seqs is pageable host memory
+  int rc = e == hipSuccess ? TVR_OK : fail(TVR_ERR_HIP, std::string("tvr_attention: ") + hipGetErrorString(e));
+  if (rc == TVR_OK)
+    rc = launch_attention(m, qkv, cache, d_seqs, n_seq, maxT, z, afmt, zf, st, zf_last != 0, zf_rows, row_from, cos_t,
+                          sin_t);
+  e = hipStreamSynchronize(st);
+  if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string("tvr_attention: ") + hipGetErrorString(e));
+  (void)hipFree(d_seqs);
+  return rc;
 }
 
 }  // extern "C"
