@@ -225,8 +225,14 @@ int tvr_trace_flush(tvr_trace* trace, void* stream);
 /* Copy a traced hook into a caller device buffer [n_tokens][d] (async on
  * `stream`): what = TVR_TRACE_RESID_PRE gives blocks.{layer}.hook_resid_pre
  * (layer == n_layers: the final residual), TVR_TRACE_Z blocks.{layer}.attn.hook_z.
- * dst needs only float alignment (4 B). */
-enum tvr_trace_hook { TVR_TRACE_RESID_PRE = 0, TVR_TRACE_Z = 1 };
+ * dst needs only float alignment (4 B).
+ * TVR_TRACE_Q / _K / _V give blocks.{layer}.attn.hook_q / hook_k / hook_v
+ * flattened over heads, BEFORE rotary (TransformerLens' hook_q, not hook_rot_q),
+ * layer in [0, n_layers): the Q | K | V columns the layer's GEMM wrote on the
+ * model's GEMM path, copied out of the trace's [tokens][3 d] rows.  hook_v
+ * carries b_V = 0, as in the processed model (fold_value_biases).
+ * (Backward-compatible addition: ABI 11.) */
+enum tvr_trace_hook { TVR_TRACE_RESID_PRE = 0, TVR_TRACE_Z = 1, TVR_TRACE_Q = 2, TVR_TRACE_K = 3, TVR_TRACE_V = 4 };
 int tvr_trace_read(const tvr_trace* trace, int32_t what, int32_t layer, float* dst,
                    void* stream);
 int32_t tvr_trace_num_tokens(const tvr_trace* trace);
@@ -251,6 +257,35 @@ int32_t tvr_trace_num_tokens(const tvr_trace* trace);
  * (Backward-compatible addition: ABI 11.) */
 int tvr_trace_capture_resid(tvr_trace* trace, const int32_t* pos, const int32_t* group,
                             int32_t n_groups, float* out, void* stream);
+/* Attention patterns of one query per traced sequence, every layer and head in
+ * one launch: out_pattern[s][l][h][j] = blocks.{l}.attn.hook_pattern[0, h, q, j]
+ * of sequence s for q = pos ? pos[s] : seq_len[s] - 1 and keys j in [0, q];
+ * columns (q, ld) are written as +0.0.  The pattern is the softmax over the keys
+ * j <= q of rot(Q[q, h]) . rot(K[j, h]) / sqrt(d_head), computed in fp32 from
+ * the Q / K rows the trace holds (TVR_TRACE_Q / _K: those of the model's GEMM
+ * path, whichever it is) with the model's rotary tables.
+ *   cls       host [n_tokens] class id per traced token in [-1, n_classes), or
+ *             NULL; n_classes in [1, 64] when cls is given
+ *   out_mass  device [n_seq][L][H][n_classes] or NULL (needs cls):
+ *             out_mass[s][l][h][c] = sum over keys j <= q of sequence s with
+ *             class c of the pattern (a key of class -1 is counted nowhere; a
+ *             class without keys gives +0.0).  Todd et al.'s cheap head signal:
+ *             where the last token attends, by token role.
+ *   out_pattern device [n_seq][L][H][ld] or NULL, ld > the largest q
+ * Both outputs are written element-wise: float alignment (4 B) suffices.
+ * Sums run in a fixed order (a lane's keys in key order, then a fixed lane
+ * tree), no atomics: results are bitwise reproducible for a given trace, and
+ * the pattern's bits do not depend on whether the mass is requested.  Runs a
+ * pending deferred clean forward first; everything is enqueued on `stream`.
+ * Timed under TVR_HBM_ATTENTION.  All arguments are validated before any device
+ * call: TVR_ERR_INVALID for a null trace, an empty trace, both outputs null,
+ * out_mass without cls, n_classes outside [1, 64] with cls given, a class
+ * outside [-1, n_classes), a pos outside [0, seq_len) or at or beyond n_ctx,
+ * ld <= the largest q with out_pattern given.  TVR_ERR_UNSUPPORTED (before any
+ * launch) if the longest key range does not fit the kernel's LDS (n_ctx beyond
+ * about 16,000).  (Backward-compatible addition: ABI 11.) */
+int tvr_trace_capture_pattern(tvr_trace* trace, const int32_t* pos, const int32_t* cls, int32_t n_classes,
+                              float* out_pattern, int32_t ld, float* out_mass, void* stream);
 
 /* Batched clean forward of n_seq prompts (ragged lengths, packed tokens).
  * Replaces the per-prompt model.forward / run_with_cache calls
@@ -445,6 +480,26 @@ int tvr_attention(tvr_model* model, int32_t fmt, const float* qkv, const float* 
                   const tvr_attn_seq* seqs, int32_t n_seq, int32_t row_from, int32_t rows,
                   int32_t cache_rows, void* z, float* zf, int32_t zf_last, int32_t zf_rows,
                   const float* cos_t, const float* sin_t, void* stream);
+/* The pattern kernel of tvr_trace_capture_pattern alone, on a caller's buffer
+ * (one layer): sequence s is the positions 0 .. qpos[s] at rows row0[s] .. of
+ * qkv, its query the row row0[s] + qpos[s].  Only the query row's Q columns and
+ * the K columns of rows [row0, row0 + qpos] are read.
+ *   qkv    device [rows][3 d]: Q | K | V per row, before rotary, 16-byte aligned
+ *   cls    host [rows] (indexed by row) in [-1, n_classes), or NULL
+ *   out_pattern device [n_seq][H][ld] or NULL; out_mass device
+ *          [n_seq][H][n_classes] or NULL; written element-wise (float alignment)
+ *   cos_t, sin_t  device [n_ctx][d_head / 4], 16-byte aligned, or both NULL:
+ *          the model's own
+ * TVR_ERR_INVALID as tvr_trace_capture_pattern, and for a null model / qkv /
+ * row0 / qpos, n_seq <= 0, rows <= 0, a qpos outside [0, n_ctx), rows
+ * [row0, row0 + qpos] outside the buffer, a qkv or table that is not 16-byte
+ * aligned, one table without the other.  A test primitive: it copies the
+ * descriptors to a temporary device buffer and synchronises `stream`.
+ * (Backward-compatible addition: ABI 11.) */
+int tvr_attention_pattern(tvr_model* model, const float* qkv, int32_t rows, const int32_t* row0,
+                          const int32_t* qpos, int32_t n_seq, const int32_t* cls, int32_t n_classes,
+                          float* out_pattern, int32_t ld, float* out_mass, const float* cos_t,
+                          const float* sin_t, void* stream);
 
 /* Kernel timing (HIP events recorded on the launch stream around every GEMM
  * launch while enabled).  tvr_profile_read synchronises the recorded events
@@ -472,7 +527,8 @@ enum tvr_hbm_kind {
   TVR_HBM_CAPTURE = 1,    /* extraction: sum of hook_z at every prompt's last row -> [d] per layer; and
                            * tvr_trace_capture_resid: rows read x (L + 1) x d x 4 + out read and written */
   TVR_HBM_LNPRE = 2,      /* LayerNormPre rows -> GEMM input format */
-  TVR_HBM_ATTENTION = 3,  /* attention: fp32 Q/K/V rows in, z out (activation format [+ fp32 hook_z]) */
+  TVR_HBM_ATTENTION = 3,  /* attention: fp32 Q/K/V rows in, z out (activation format [+ fp32 hook_z]); and
+                           * tvr_trace_capture_pattern: per layer the Q row + the K rows read, pattern / mass written */
   TVR_HBM_ROW_STATS = 4,  /* softmax target probability / top-k over one logit row per site */
   TVR_HBM_LIN_ENTRY = 5,  /* linearised entry layer of REPLACE_HEAD sites (the vectors' W1 product G and
                            * the K = d_head entry-row GEMM with its combine epilogue): entering rows' outputs

@@ -17,8 +17,9 @@ from .experiments import (apply_layered_vectors_to_zero_shot, apply_layered_vect
                           extract_task_vectors, assemble_end_list_tasks, assemble_task_vector, calculate_average_causal_indirect_effect,
                           check_accuracy_of_added_task_vector, check_accuracy_of_task_vector,
                           gather_head_activations_to_layers, generate_mean_activation, generate_shuffled_prompt,
-                          generate_shuffled_prompts, head_ablation_curve, joint_head_patch_effect,
-                          logits_to_next_k_tokens, substitute_task, test_component_hypothesis)
+                          generate_shuffled_prompts, head_ablation_curve, head_attention_profile,
+                          joint_head_patch_effect, logits_to_next_k_tokens, substitute_task,
+                          test_component_hypothesis, top_attention_heads)
 
 __version__ = "0.1.0"
 SUBMODULES = ("_lib", "config", "tasks", "tokenizer", "weights", "prompts", "model", "experiments",

@@ -30,6 +30,9 @@ TVR_ERR_INTERNAL = -6
 # enum tvr_trace_hook
 TRACE_RESID_PRE = 0
 TRACE_Z = 1
+TRACE_Q = 2  # blocks.{l}.attn.hook_q / hook_k / hook_v, before rotary
+TRACE_K = 3
+TRACE_V = 4
 
 # enum tvr_site_kind
 SITE_NONE = 0
@@ -162,6 +165,11 @@ SIGNATURES = {
     "tvr_attention": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, c_f32p,
                                      ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p]),
+    "tvr_attention_pattern": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int32, c_i32p, c_i32p, ctypes.c_int32,
+                                             c_i32p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p, c_f32p, c_f32p,
+                                             ctypes.c_void_p]),
+    "tvr_trace_capture_pattern": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, ctypes.c_int32, c_f32p,
+                                                 ctypes.c_int32, c_f32p, ctypes.c_void_p]),
 }
 
 OPS_PATH = LIB_PATH.parent / OPS_NAME
@@ -171,6 +179,10 @@ OPS = ("forward_clean", "patch_sweep", "project_heads", "forward_logits")
 SET_OPS = ("patch_sweep_sets",)
 # the grouped residual capture (tvr_trace_capture_resid), registered by the same extension
 RESID_OPS = ("capture_resid",)
+# one query's attention pattern / per-class attention mass per traced sequence (tvr_trace_capture_pattern)
+PATTERN_OPS = ("capture_pattern",)
+# tvr_trace_capture_pattern's upper limit on n_classes (include/tvr.h)
+PATTERN_MAX_CLASSES = 64
 
 _LIB = None
 _OPS_LOADED = False

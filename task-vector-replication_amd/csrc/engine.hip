@@ -25,6 +25,7 @@
 #include "tvr.h"
 #include "gemm_f32.hpp"
 #include "attention_mfma.hpp"
+#include "attention_pattern.hpp"
 #include "gemm_pingpong.hpp"
 #include "gemm_skinny.hpp"
 #include "gemm_planar.hpp"
@@ -1158,6 +1159,55 @@ int launch_attention(tvr_model* m, const float* qkv, const float* cache_qkv, con
   return TVR_OK;
 }
 
+// attention_pattern_kernel over n_layers slabs of `qkv` (slab stride layer_stride floats, rows of 3 d floats):
+// one wave per (sequence, head), the layer on grid.y.  max_keys: the longest qpos + 1 (sizes the LDS).
+// Everything the kernel cannot take is refused here, before the launch.
+int launch_pattern(tvr_model* m, const char* fn, const float* qkv, size_t layer_stride, int n_layers,
+                   const PatternSeq* d_seqs, int n_seq, int max_keys, const int32_t* d_cls, int n_classes,
+                   float* out_pattern, int ld, float* out_mass, const float* cos_t, const float* sin_t,
+                   hipStream_t st) {
+  const tvr_config& c = m->cfg;
+  const int d = c.d_model, dh = c.d_head;
+  const size_t lds = pattern_lds_bytes(dh, max_keys);
+  if (!(dh == 16 || dh == 64 || dh == 80 || dh == 128) || c.rotary_dim * 4 != dh)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": the pattern kernel covers d_head 16 / 64 / 80 / 128 with "
+                                                       "rotary_dim = d_head / 4");
+  if (lds > 64 * 1024)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": " + std::to_string(max_keys) + " keys do not fit the "
+                                                       "kernel's 64 KiB of LDS scores");
+  if ((int64_t)n_seq * c.n_heads > INT_MAX || n_layers > 65535)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": too many (sequence, head) pairs or layers for one launch");
+  const float* rot_cos = cos_t ? cos_t : m->rot_cos;
+  const float* rot_sin = sin_t ? sin_t : m->rot_sin;
+  const float inv_scale = 1.0f / std::sqrt((float)dh);
+  const dim3 grid((unsigned)(n_seq * c.n_heads), (unsigned)n_layers), block(64);
+#define TVR_PATTERN(DHV)                                                                                          \
+  hipLaunchKernelGGL((attention_pattern_kernel<DHV>), grid, block, lds, st, qkv, layer_stride, 3 * d, d_seqs,      \
+                     c.n_heads, d_cls, n_classes, out_pattern, ld, out_mass, rot_cos, rot_sin, d, inv_scale)
+  if (dh == 16) { TVR_PATTERN(16); } else if (dh == 64) { TVR_PATTERN(64); }
+  else if (dh == 80) { TVR_PATTERN(80); } else { TVR_PATTERN(128); }
+#undef TVR_PATTERN
+  TVR_HIP(hipGetLastError());
+  return TVR_OK;
+}
+
+// The argument checks tvr_attention_pattern and tvr_trace_capture_pattern share (host only); `fn` prefixes
+// the message.  n_cls: entries of cls.
+int check_pattern_args(const char* fn, const int32_t* cls, int n_cls, int32_t n_classes, const float* out_pattern,
+                       const float* out_mass) {
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!out_pattern && !out_mass) return bad("out_pattern and out_mass are both null");
+  if (out_mass && !cls) return bad("out_mass needs cls");
+  if (cls) {
+    if (n_classes <= 0 || n_classes > PATTERN_MAX_CLASSES)
+      return bad("n_classes must be in [1, " + std::to_string(PATTERN_MAX_CLASSES) + "]");
+    for (int r = 0; r < n_cls; ++r)
+      if (cls[r] < -1 || cls[r] >= n_classes)
+        return bad("class of row " + std::to_string(r) + " outside [-1, n_classes)");
+  }
+  return TVR_OK;
+}
+
 // One transformer block over the first R rows (Pythia parallel residual):
 //   x = LNPre(resid); [qkv | h] = x @ W1^T + b1; z = attn(qkv); resid += [z|gelu h] @ W2^T + b2
 // (run_block computes up to z; run_block_out the second projection.)
@@ -1866,6 +1916,14 @@ int tvr_trace_read(const tvr_trace* t, int32_t what, int32_t layer, float* dst, 
   const float* src = nullptr;
   if (what == TVR_TRACE_RESID_PRE && layer >= 0 && layer <= L) src = t->resid + layer * stride;
   if (what == TVR_TRACE_Z && layer >= 0 && layer < L) src = t->z + layer * stride;
+  if (what >= TVR_TRACE_Q && what <= TVR_TRACE_V && layer >= 0 && layer < L) {
+    // hook_q / hook_k / hook_v (before rotary): columns [(what - Q) d, .. + d) of the layer's [tokens][3 d] rows
+    if (t->n_tokens > 0)
+      TVR_HIP(hipMemcpy2DAsync(dst, (size_t)d * sizeof(float), t->qkv + layer * 3 * stride + (what - TVR_TRACE_Q) * d,
+                               (size_t)3 * d * sizeof(float), (size_t)d * sizeof(float), (size_t)t->n_tokens,
+                               hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return TVR_OK;
+  }
   if (!src) return fail(TVR_ERR_INVALID, "tvr_trace_read: bad hook/layer");
   if (what == TVR_TRACE_RESID_PRE && t->uncentred && t->n_tokens > 0) {
     // TL's residual stream is centred (every write to it is: W_E, W_O, W_out, their biases); the x16 path's
@@ -1963,6 +2021,49 @@ int tvr_trace_capture_resid(tvr_trace* t, const int32_t* pos, const int32_t* gro
   }
   // rows read x (L + 1) x d x 4, plus out read and written
   ps.done(TVR_HBM_CAPTURE, ((double)n_seq + 2.0 * n_groups) * (L + 1) * d * 4.0);
+  return TVR_OK;
+}
+
+int tvr_trace_capture_pattern(tvr_trace* t, const int32_t* pos, const int32_t* cls, int32_t n_classes,
+                              float* out_pattern, int32_t ld, float* out_mass, void* stream) {
+  const char* fn = "tvr_trace_capture_pattern";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!t) return bad("null trace");
+  if (t->n_seq <= 0) return bad("trace is empty: run tvr_forward_clean first");
+  TVR_TRY(check_pattern_args(fn, cls, t->n_tokens, n_classes, out_pattern, out_mass));
+  tvr_model* m = t->model;
+  const tvr_config& c = m->cfg;
+  const int L = c.n_layers, d = c.d_model, H = c.n_heads, n_seq = t->n_seq;
+  std::vector<PatternSeq> seqs(n_seq);
+  int max_q = 0;
+  double keys = 0.0;
+  for (int s = 0; s < n_seq; ++s) {
+    const int q = pos ? pos[s] : t->seq_len[s] - 1;
+    if (q < 0 || q >= t->seq_len[s] || q >= c.n_ctx)
+      return bad("pos of sequence " + std::to_string(s) + " out of range");
+    seqs[s] = PatternSeq{t->seq_off[s], q};
+    max_q = std::max(max_q, q);
+    keys += q + 1;
+  }
+  if (out_pattern && ld <= max_q) return bad("ld must exceed the largest query position (" + std::to_string(max_q) + ")");
+  hipStream_t st = (hipStream_t)stream;
+  TVR_TRY(flush_pending(t, stream));  // a deferred clean forward runs now (it uses the workspace: carve after it)
+  Carve cv;
+  const size_t o_seqs = cv.take<PatternSeq>(seqs.size());
+  const size_t o_cls = out_mass ? cv.take<int32_t>((size_t)t->n_tokens) : 0;
+  TVR_TRY(ensure_workspace(m, cv.off, st));
+  char* base = m->ws;
+  UploadBatch ub;
+  ub.add(o_seqs, seqs);
+  if (out_mass) ub.add(o_cls, std::vector<int32_t>(cls, cls + t->n_tokens));
+  TVR_TRY(flush_uploads(m, st, base, ub));
+  ProfSpan ps(m, st);
+  TVR_TRY(launch_pattern(m, fn, t->qkv, (size_t)3 * t->max_tokens * d, L, (const PatternSeq*)(base + o_seqs), n_seq,
+                         max_q + 1, out_mass ? (const int32_t*)(base + o_cls) : nullptr, n_classes, out_pattern, ld,
+                         out_mass, nullptr, nullptr, st));
+  // per layer: every sequence's Q row and its K rows [0, qpos] in, the pattern rows and the class sums out
+  ps.done(TVR_HBM_ATTENTION, 4.0 * L * ((n_seq + keys) * d + (double)n_seq * H * ((out_pattern ? ld : 0) +
+                                                                                   (out_mass ? n_classes : 0))));
   return TVR_OK;
 }
 
@@ -2763,6 +2864,54 @@ int tvr_attention(tvr_model* m, int32_t fmt, const float* qkv, const float* cach
   e = hipStreamSynchronize(st);
   if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string("tvr_attention: ") + hipGetErrorString(e));
   (void)hipFree(d_seqs);
+  return rc;
+}
+
+int tvr_attention_pattern(tvr_model* m, const float* qkv, int32_t rows, const int32_t* row0, const int32_t* qpos,
+                          int32_t n_seq, const int32_t* cls, int32_t n_classes, float* out_pattern, int32_t ld,
+                          float* out_mass, const float* cos_t, const float* sin_t, void* stream) {
+  // every check on the host, before any device call
+  const char* fn = "tvr_attention_pattern";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!m) return bad("null model");
+  if (!qkv) return bad("null qkv");
+  if (!row0 || !qpos) return bad("null row0 / qpos");
+  if (n_seq <= 0) return bad("n_seq must be positive");
+  if (rows <= 0) return bad("rows must be positive");
+  TVR_TRY(check_pattern_args(fn, cls, rows, n_classes, out_pattern, out_mass));
+  if ((cos_t == nullptr) != (sin_t == nullptr)) return bad("cos_t and sin_t must both be given or both be null");
+  if (((uintptr_t)qkv | (uintptr_t)cos_t | (uintptr_t)sin_t) & 15)
+    return bad("qkv and the rotary tables must be 16-byte aligned");
+  std::vector<PatternSeq> seqs(n_seq);
+  int max_q = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    const std::string at = " (sequence " + std::to_string(s) + ")";
+    if (qpos[s] < 0 || qpos[s] >= m->cfg.n_ctx) return bad("qpos outside [0, n_ctx)" + at);
+    if (row0[s] < 0 || (int64_t)row0[s] + qpos[s] >= rows) return bad("rows [row0, row0 + qpos] outside the qkv buffer" + at);
+    seqs[s] = PatternSeq{row0[s], qpos[s]};
+    max_q = std::max(max_q, qpos[s]);
+  }
+  if (out_pattern && ld <= max_q) return bad("ld must exceed the largest query position (" + std::to_string(max_q) + ")");
+  const hipStream_t st = (hipStream_t)stream;
+  // descriptors, then the classes, in one temporary buffer
+  const size_t seq_bytes = align_up((size_t)n_seq * sizeof(PatternSeq));
+  const size_t cls_bytes = out_mass ? (size_t)rows * sizeof(int32_t) : 0;
+  char* dbuf = nullptr;
+  if (hipMalloc(&dbuf, seq_bytes + cls_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TVR_ERR_NOMEM, std::string(fn) + ": descriptor buffer");
+  }
+  hipError_t e = hipMemcpyAsync(dbuf, seqs.data(), (size_t)n_seq * sizeof(PatternSeq), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && cls_bytes) e = hipMemcpyAsync(dbuf + seq_bytes, cls, cls_bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // pageable host memory
+  int rc = e == hipSuccess ? TVR_OK : fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  if (rc == TVR_OK)
+    rc = launch_pattern(m, fn, qkv, 0, 1, (const PatternSeq*)dbuf, n_seq, max_q + 1,
+                        cls_bytes ? (const int32_t*)(dbuf + seq_bytes) : nullptr, n_classes, out_pattern, ld, out_mass,
+                        cos_t, sin_t, st);
+  e = hipStreamSynchronize(st);
+  if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  (void)hipFree(dbuf);
   return rc;
 }
 

@@ -10,6 +10,7 @@
 //   tvr::project_heads   tvr_project_heads               (scratch2.py:97-98)
 //   tvr::forward_logits  tvr_forward_logits              (scratch.py:143,206,209)
 //   tvr::capture_resid   tvr_trace_capture_resid         (run_with_cache + hook_resid_pre[l][0, pos], summed)
+//   tvr::capture_pattern tvr_trace_capture_pattern       (run_with_cache + cache["pattern", l][0, :, pos, :])
 //
 // Every op enqueues on torch's CURRENT stream of the output device and
 // allocates its outputs through torch's caching allocator; host arrays
@@ -221,6 +222,40 @@ at::Tensor& capture_resid(int64_t trace, const std::optional<at::Tensor>& pos, c
   return out;
 }
 
+// One query's attention pattern per traced sequence, every layer and head (tvr_trace_capture_pattern).  pos: CPU
+// int32 [n_seq] or None (last position); cls: CPU int32 [traced tokens] or None; out_pattern [n_seq, L, H, ld] and
+// out_mass [n_seq, L, H, n_classes]: contiguous fp32 device tensors (offset views are fine: float alignment
+// suffices), at least one of them.  The façade sizes them from the trace's model.
+void capture_pattern(int64_t trace, const std::optional<at::Tensor>& pos, const std::optional<at::Tensor>& cls,
+                     int64_t n_classes, int64_t n_seq, int64_t n_layers, int64_t n_heads,
+                     const std::optional<at::Tensor>& out_pattern, const std::optional<at::Tensor>& out_mass) {
+  TORCH_CHECK_VALUE(trace != 0, "tvr: capture_pattern needs a trace");
+  TORCH_CHECK_VALUE(out_pattern.has_value() || out_mass.has_value(), "tvr: capture_pattern needs out_pattern or out_mass");
+  TORCH_CHECK_VALUE(!pos.has_value() || pos->numel() == n_seq, "tvr: pos must have one entry per traced sequence");
+  TORCH_CHECK_VALUE(!out_mass.has_value() || cls.has_value(), "tvr: out_mass needs cls");
+  TORCH_CHECK_VALUE(!cls.has_value() || n_classes > 0, "tvr: n_classes must be positive");
+  const c10::Device dev = out_pattern.has_value() ? out_pattern->device() : out_mass->device();
+  need_gpu(dev);
+  auto shaped = [&](const at::Tensor& t, int64_t last) {
+    return t.device() == dev && t.scalar_type() == at::kFloat && t.is_contiguous() && t.dim() == 4 &&
+           t.size(0) == n_seq && t.size(1) == n_layers && t.size(2) == n_heads && (last < 0 || t.size(3) == last);
+  };
+  TORCH_CHECK_VALUE(!out_pattern.has_value() || shaped(*out_pattern, -1),
+                    "tvr: out_pattern must be a contiguous fp32 tensor [n_seq, n_layers, n_heads, ld]");
+  TORCH_CHECK_VALUE(!out_mass.has_value() || shaped(*out_mass, n_classes),
+                    "tvr: out_mass must be a contiguous fp32 tensor [n_seq, n_layers, n_heads, n_classes]");
+  auto* tr = reinterpret_cast<tvr_trace*>(static_cast<intptr_t>(trace));
+  // the C ABI trusts cls to hold one entry per traced token: check it against the tensor here
+  TORCH_CHECK_VALUE(!cls.has_value() || cls->numel() == tvr_trace_num_tokens(tr),
+                    "tvr: cls must have one entry per traced token");
+  DeviceGuard guard(dev);
+  check(tvr_trace_capture_pattern(tr, opt_host_i32(pos, "pos"), opt_host_i32(cls, "cls"), (int32_t)n_classes,
+                                  out_pattern.has_value() ? out_pattern->data_ptr<float>() : nullptr,
+                                  out_pattern.has_value() ? (int32_t)out_pattern->size(3) : 0,
+                                  out_mass.has_value() ? out_mass->data_ptr<float>() : nullptr, cur_stream(dev)),
+        "tvr_trace_capture_pattern");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tvr, m) {
@@ -235,6 +270,8 @@ TORCH_LIBRARY(tvr, m) {
   m.def("forward_logits(int model, Tensor? tokens, Tensor? resid, int start_layer, Tensor seq_lens, int d_vocab, "
         "Device device) -> Tensor");
   m.def("capture_resid(int trace, Tensor? pos, Tensor? groups, int n_groups, int n_seq, Tensor(a!) out) -> Tensor(a!)");
+  m.def("capture_pattern(int trace, Tensor? pos, Tensor? cls, int n_classes, int n_seq, int n_layers, int n_heads, "
+        "Tensor(a!)? out_pattern, Tensor(b!)? out_mass) -> ()");
 }
 
 // Mixed host / device tensor arguments: one implementation for every backend key.
@@ -245,4 +282,5 @@ TORCH_LIBRARY_IMPL(tvr, CompositeExplicitAutograd, m) {
   m.impl("project_heads", &project_heads);
   m.impl("forward_logits", &forward_logits);
   m.impl("capture_resid", &capture_resid);
+  m.impl("capture_pattern", &capture_pattern);
 }

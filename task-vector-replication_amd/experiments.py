@@ -28,6 +28,11 @@ position layer by layer):
   extract_task_vectors, apply_task_vectors_to_zero_shot,
   apply_task_vectors_to_zero_shot_by_probability
 
+and the cheap head signal of Todd et al., the last token's attention by token
+role (one pass over the trace's Q / K rows, no patched forward):
+
+  head_attention_profile, top_attention_heads
+
 Drop-in notes
 * ``model`` is an ``amd.Model`` instead of a HookedTransformer; it must be
   passed (the reference's defaults bind a module-global model).
@@ -49,7 +54,8 @@ import torch
 from . import _lib
 from .model import Model, make_sites, range_checked
 from .prompts import (Pairs, assemble_end_list_tasks, construct_query, generate_shuffled_prompt,  # noqa: F401
-                      generate_shuffled_prompts, icl_multi_token, icl_single_token, sample_icl_prompts)
+                      ROLES, generate_shuffled_prompts, icl_multi_token, icl_single_token, sample_icl_prompts,
+                      sample_icl_prompts_with_roles)
 
 # Sites per patch_sweep launch (bounds the activation workspace: a CIE site
 # of a T-token prompt holds T rows).
@@ -270,6 +276,56 @@ def apply_task_vectors_to_zero_shot_by_probability(task_vectors: torch.Tensor, c
     [n_layers] on the device."""
     rows = _task_vector_rows(task_vectors, model.cfg)
     return _zero_shot_dprob(rows, contexts, function_token, model, False, kind=_lib.SITE_SET_RESID_PRE_VEC)
+
+
+# ---------------------------------------------------- attention by token role
+@range_checked
+def head_attention_profile(contexts: Pairs, function_token: str, seperator_token: Optional[str] = None,
+                           model: Model = None, num_contexts: int = 256, len_contexts: int = 4) -> torch.Tensor:
+    """Where the last token of an ICL prompt attends, per head: the mean over
+    ``num_contexts`` prompts (the prompt stream of ``generate_mean_activation``)
+    of ``blocks.{l}.attn.hook_pattern[0, h, -1, :]`` summed over the tokens of
+    each role of ``prompts.ROLES``.  [n_layers, n_heads, len(ROLES)] on the
+    device; every (l, h) row sums to 1.  The cheap companion of
+    ``calculate_average_causal_indirect_effect`` (Todd et al. describe
+    function-vector heads by their attention to the demonstrations' labels):
+    one clean forward into a trace and one pass over its Q / K rows
+    (``Trace.attention_mass``) per ``EXTRACT_BATCH`` prompts, no patched
+    forward."""
+    if num_contexts <= 0:
+        raise ValueError("num_contexts must be positive")
+    if len_contexts < 0 or len_contexts >= len(contexts):
+        raise ValueError("len_contexts must be smaller than the number of contexts (demos + one query)")
+    prompts, roles = sample_icl_prompts_with_roles(model, contexts, function_token, seperator_token, num_contexts,
+                                                   len_contexts)
+    total = None
+    for a, b in _chunks(len(prompts), EXTRACT_BATCH):
+        seqs = prompts[a:b]
+        trace = model._sweep_trace(len(seqs), sum(len(s) for s in seqs))
+        model.forward_clean(seqs, trace=trace)
+        mass = trace.attention_mass(roles[a:b], len(ROLES)).sum(0)  # prompts in order: reproducible
+        total = mass if total is None else total + mass
+    return total / num_contexts
+
+
+def top_attention_heads(profile: torch.Tensor, role, num_heads: int) -> List[Tuple[int, int]]:
+    """The ``num_heads`` (layer, head) pairs of a ``head_attention_profile``
+    that put the most attention on ``role`` (a name of ``prompts.ROLES`` or its
+    index), highest first (torch.topk's order and tie rule, as
+    ``top_cie_heads``)."""
+    if not isinstance(profile, torch.Tensor) or profile.dim() != 3 or profile.shape[2] != len(ROLES):
+        raise ValueError("profile must be of shape (n_layers, n_heads, len(ROLES))")
+    if isinstance(role, str):
+        if role not in ROLES:
+            raise ValueError(f"role must be one of {ROLES}")
+        role = ROLES.index(role)
+    if not 0 <= int(role) < len(ROLES):
+        raise ValueError(f"role must be one of {ROLES} or its index")
+    H = profile.shape[1]
+    if not 0 < num_heads <= profile.shape[0] * H:
+        raise ValueError("num_heads must be in [1, n_layers * n_heads]")
+    _, idx = torch.topk(profile[:, :, int(role)].flatten(), num_heads)
+    return [(int(i) // H, int(i) % H) for i in idx.tolist()]
 
 
 # ------------------------------------------------------------------- a6 / a7

@@ -133,6 +133,36 @@ class Trace:
         """``blocks.{layer}.attn.hook_z`` flattened over heads ([tokens, d])."""
         return self._read(_lib.TRACE_Z, layer)
 
+    def q(self, layer: int) -> torch.Tensor:
+        """``blocks.{layer}.attn.hook_q`` flattened over heads ([tokens, d]),
+        before rotary (TransformerLens' ``hook_q``, not ``hook_rot_q``)."""
+        return self._read(_lib.TRACE_Q, layer)
+
+    def k(self, layer: int) -> torch.Tensor:
+        """``blocks.{layer}.attn.hook_k`` flattened over heads ([tokens, d]), before rotary."""
+        return self._read(_lib.TRACE_K, layer)
+
+    def v(self, layer: int) -> torch.Tensor:
+        """``blocks.{layer}.attn.hook_v`` flattened over heads ([tokens, d]);
+        ``b_V`` is zero, as in the processed model (``fold_value_biases``)."""
+        return self._read(_lib.TRACE_V, layer)
+
+    def attention_pattern(self, pos: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """``blocks.{l}.attn.hook_pattern[0, h, pos[s], :]`` of every traced
+        sequence ``s``, layer and head: ``[n_seq, L, H, max(pos) + 1]``, zero
+        beyond each sequence's query position.  ``pos`` defaults to every
+        sequence's last position.  Replaces one ``run_with_cache`` per prompt
+        and ``cache["pattern", l][0, :, -1, :]`` per layer."""
+        return self.model.capture_pattern(self, positions=pos, want_pattern=True)[0]
+
+    def attention_mass(self, classes, n_classes: int, pos: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """The attention the query position ``pos[s]`` of every traced sequence
+        pays to each class of keys: ``[n_seq, L, H, n_classes]`` with
+        ``[s, l, h, c] = Σ_{j <= pos[s], classes[s][j] == c} pattern[s, l, h, j]``.
+        ``classes``: one id in ``[-1, n_classes)`` per traced token, flat or
+        one list per sequence; ``-1`` is counted nowhere."""
+        return self.model.capture_pattern(self, positions=pos, classes=classes, n_classes=n_classes)[1]
+
     def _read(self, what: int, layer: int) -> torch.Tensor:
         m = self.model
         buf = torch.empty(sum(self.seq_lens), m.cfg.d_model, device=m.device)
@@ -559,6 +589,55 @@ class Model(TokenizerMixin):
         self._check_range("tvr_trace_capture_resid")  # (a deferred clean forward may have run)
         trace._pending_out = None
         return out
+
+    def capture_pattern(self, trace: Trace, positions: Optional[Sequence[int]] = None, classes=None,
+                        n_classes: int = 0, want_pattern: bool = False):
+        """One query's attention pattern per traced sequence, every layer and
+        head, from the Q / K rows ``trace`` holds (tvr_trace_capture_pattern):
+        ``(pattern, mass)`` with ``pattern`` ``[n_seq, L, H, max(positions) + 1]``
+        (``want_pattern``, else ``None``) and ``mass`` ``[n_seq, L, H, n_classes]``
+        (``classes`` given, else ``None``); see ``Trace.attention_pattern`` and
+        ``Trace.attention_mass``.  Every argument is checked before the engine
+        is called.  Bitwise reproducible for a given trace."""
+        if trace.model is not self:
+            raise ValueError("trace belongs to another model")
+        lens = np.asarray(trace.seq_lens, dtype=np.int64)
+        n = int(lens.shape[0])
+        if n == 0:
+            raise ValueError("trace is empty: run forward_clean(trace=...) first")
+        if not want_pattern and classes is None:
+            raise ValueError("nothing to capture: ask for the pattern or give classes")
+        pos = None
+        if positions is not None:
+            pos = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1)
+            if pos.shape[0] != n:
+                raise ValueError("positions must have one entry per traced sequence")
+            if np.any(pos < 0) or np.any(pos >= lens):
+                raise ValueError("a position lies outside its sequence")
+        cls = None
+        if classes is not None:
+            n_classes = int(n_classes)
+            if not 0 < n_classes <= _lib.PATTERN_MAX_CLASSES:
+                raise ValueError(f"n_classes must be in [1, {_lib.PATTERN_MAX_CLASSES}]")
+            if len(classes) == n and all(not np.isscalar(c) for c in classes):  # one list per sequence
+                if any(len(c) != t for c, t in zip(classes, lens)):
+                    raise ValueError("classes must have one entry per traced token")
+                classes = [x for c in classes for x in c]
+            cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+            if cls.shape[0] != int(lens.sum()):
+                raise ValueError("classes must have one entry per traced token")
+            if np.any(cls < -1) or np.any(cls >= n_classes):
+                raise ValueError("a class lies outside [-1, n_classes)")
+        cfg = self.cfg
+        ld = int(pos.max() if pos is not None else lens.max() - 1) + 1
+        pattern = torch.empty(n, cfg.n_layers, cfg.n_heads, ld, device=self.device) if want_pattern else None
+        mass = torch.empty(n, cfg.n_layers, cfg.n_heads, n_classes, device=self.device) if cls is not None else None
+        self._op("capture_pattern", trace._h.value, torch.from_numpy(pos) if pos is not None else None,
+                 torch.from_numpy(cls) if cls is not None else None, n_classes if cls is not None else 0, n,
+                 cfg.n_layers, cfg.n_heads, pattern, mass)
+        self._check_range("tvr_trace_capture_pattern")  # (a deferred clean forward may have run)
+        trace._pending_out = None
+        return pattern, mass
 
     def project_heads(self, zsum: torch.Tensor) -> torch.Tensor:
         """[L, d] z-sums → [L, H, d] hook_result sums."""

@@ -61,6 +61,58 @@ def sample_icl_prompts(model, contexts: Pairs, function_token: str, separator: O
     return prompts
 
 
+# Token roles of an ICL prompt (the classes of ``Trace.attention_mass`` /
+# ``experiments.head_attention_profile``): where the last token attends.
+# "self" is the prompt's last token, the query's function token, i.e. the
+# query position itself; when the function token is several tokens long, the
+# ones before the last belong to "query_input".
+ROLES = ("bos", "demo_input", "demo_function", "demo_label", "separator", "query_input", "self")
+_BOS, _DIN, _DFN, _DLB, _SEP, _QIN, _SELF = range(len(ROLES))
+
+
+def _icl_roles(n_demo_parts: Sequence[Tuple[int, int, int]], n_tail: int, n_query: int, n_f: int) -> List[int]:
+    out = [_BOS]
+    for nx, nf, ny in n_demo_parts:
+        out += [_DIN] * nx + [_DFN] * nf + [_DLB] * ny + [_SEP] * n_tail
+    return out + [_SEP] * n_tail + [_QIN] * (n_query + n_f - 1) + [_SELF]
+
+
+def icl_single_token_roles(model, demos: Pairs, query: str, function_token: str = "→",
+                           separator: Optional[str] = None) -> List[int]:
+    """One index into ``ROLES`` per token of ``icl_single_token``'s prompt for
+    the same arguments (which must be single tokens, as there)."""
+    one = model.to_single_token
+    for item in [function_token, query] + [t for pair in demos for t in pair] + \
+            ([separator] if separator is not None else []):
+        one(item)
+    return _icl_roles([(1, 1, 1)] * len(demos), 0 if separator is None else 1, 1, 1)
+
+
+def icl_multi_token_roles(model, demos: Pairs, query: str, function_token: str = "→",
+                          separator: Optional[str] = None) -> List[int]:
+    """One index into ``ROLES`` per token of ``icl_multi_token``'s prompt for
+    the same arguments."""
+    enc = model.tokenizer.encode
+    n_f = len(enc(function_token))
+    n_tail = len(enc(separator)) if separator is not None else 0
+    return _icl_roles([(len(enc(x)), n_f, len(enc(y))) for x, y in demos], n_tail, len(enc(query)), n_f)
+
+
+def sample_icl_prompts_with_roles(model, contexts: Pairs, function_token: str, separator: Optional[str],
+                                  num_contexts: int, len_contexts: int) -> Tuple[List[List[int]], List[List[int]]]:
+    """``sample_icl_prompts`` and the role of every token: the same draws from
+    the global ``random`` in the same order, so the same seed gives the same
+    prompts.  Returns (prompts, roles), ``roles[i][j]`` an index into ``ROLES``."""
+    pool = list(contexts)
+    prompts, roles = [], []
+    for _ in range(num_contexts):
+        random.shuffle(pool)
+        args = (model, pool[:len_contexts], pool[len_contexts][0], function_token, separator)
+        prompts.append(icl_multi_token(*args))
+        roles.append(icl_multi_token_roles(*args))
+    return prompts, roles
+
+
 def generate_shuffled_prompt(contexts: Pairs, model, function_token: str = ":",
                              seperator_token: Optional[str] = None) -> Tuple[str, List[int]]:
     """scratch2.py:200-211: answers of the demos permuted, the last pair is the
