@@ -500,6 +500,92 @@ int tvr_attention_pattern(tvr_model* model, const float* qkv, int32_t rows, cons
                           const int32_t* qpos, int32_t n_seq, const int32_t* cls, int32_t n_classes,
                           float* out_pattern, int32_t ld, float* out_mass, const float* cos_t,
                           const float* sin_t, void* stream);
+/* One planar GEMM through the engine's own dispatch (launch_gemm: the skinny
+ * kernel, gemm_pingpong_kernel plain, split over K, with a split tail or
+ * stream-K and their reduce kernels), C = A W^T under one fused epilogue.  The
+ * split-K workspace lives on the model; a tiny model is enough, its weights are
+ * not used.
+ *   fmt      TVR_GEMM_X2F16, TVR_ACT_X2F16_IL or TVR_GEMM_BF16: A (and a2) in
+ *            the format tvr_act_rows describes, row stride 2 lda halves
+ *   exact16  0: W planes from tvr_weight_planes (X2F16 [2][.][ldw], plane
+ *            stride wps, of w * w_scale; BF16 one plane, w_scale unused);
+ *            1: ONE fp16 plane of w * w_scale holding the weights exactly
+ *            (x2f16 formats only: two products per slice).  The interleaved
+ *            layout with two weight planes runs only the plain bias launch.
+ *   epi      TVR_EPI_BIAS   out0[r][c] = acc + bias[c]
+ *            TVR_EPI_GELU   c < n_split as TVR_EPI_BIAS; else erf-GELU(acc +
+ *                           bias) in the activation format (the layout follows
+ *                           fmt) at out1h, row stride ld1h halves, column
+ *                           c - n_split, plane stride ps1h (planar X2F16 only);
+ *                           rows < raw_rows also store acc + bias (fp32) at
+ *                           raw[r][c - n_split] (ld_raw); *range_flag |= 1 if a
+ *                           GELU value leaves the x2f16 range
+ *            TVR_EPI_RESID  out0 = acc + bias + resid[r][c] (ldr)
+ *            out0m (bias, GELU): output rows < mirror_rows of the fp32 columns
+ *            are also written to out0m (row stride ld0).  bias, range_flag,
+ *            raw, out0m may be NULL.
+ *   a_rows   host [M] or NULL: launch row r reads row a_rows[r] of A / a2
+ *            (a buffer of a_buf_rows rows)
+ *   out_rows host [M] or NULL, distinct: launch row r is row out_rows[r] of
+ *            out0, out0m, out1h and resid (buffers of out_buf_rows rows)
+ *   a2, a2_col  column tiles whose first column is >= a2_col (a multiple of
+ *            256) read a2 instead of A
+ *   skinny   opt in to the skinny kernel (taken for M <= 16 on two weight
+ *            planes, planar layout, bias epilogue, no out_rows / a2)
+ *   form     TVR_FORM_PLAN: the engine's own plan for (M, N, K) (plan_pp_cached,
+ *            as a block calls it; tvr_gemm_plan reports it); forced forms:
+ *            TVR_FORM_PLAIN; TVR_FORM_SPLITK every tile split form_n ways;
+ *            TVR_FORM_TAIL tiles [0, form_tile) plain, the rest split form_n
+ *            ways; TVR_FORM_STREAMK tiles [0, form_tile) plain, the rest
+ *            stream-K over form_n blocks
+ *   slicing  the x2f16 sliced accumulation: TVR_SLICE_MODEL the engine's rule
+ *            (K or the model's K2 >= 16384), TVR_SLICE_ON, TVR_SLICE_OFF
+ * All arguments are validated on the host before any device call and before
+ * the model is read: TVR_ERR_INVALID for a null model / args / A / W / out0, an
+ * unknown fmt, exact16, epi, form, slicing or skinny, M, N or K <= 0, K not a
+ * multiple of the k-tile (32; BF16 64), w_scale not positive and finite, lda <
+ * K or not a multiple of 8 (32 interleaved), ldw < K or not a multiple of 8,
+ * wps too small or not a multiple of 8, ld0 < N, a data buffer that is not
+ * 16-byte aligned, an a_rows / out_rows entry outside its buffer or an output
+ * row named twice, a2_col not a multiple of 256, the residual epilogue without
+ * resid, with ldr < N or with out0m, mirror_rows or raw_rows outside their
+ * rows, raw with out_rows, n_split outside [0, N], GELU strides too small for
+ * the columns (or, with N and every stride a multiple of 4 — the vector
+ * epilogue — ld1h, ps1h, n_split not multiples of 8, ld_raw not of 4), exact16
+ * with BF16, the interleaved layout with two weight planes and anything but
+ * the plain bias launch, skinny with a forced split, a mirror or another
+ * epilogue; a forced split or stream-K without the vector epilogue, form_tile
+ * outside the raster of 256 x 256 tiles, a split S < 2 or with fewer than 8
+ * k-tiles per part or more than 4096 partial tiles, stream-K blocks below the
+ * tile count, above 256 or above tiles x k-tiles.  The fused-statistics
+ * epilogue is not reachable here.  A test primitive: it copies the row
+ * indices to a temporary device buffer and synchronises `stream`.
+ * (Backward-compatible addition: ABI 11.) */
+enum tvr_gemm_epi { TVR_EPI_BIAS = 0, TVR_EPI_GELU = 1, TVR_EPI_RESID = 2 };
+enum tvr_gemm_form { TVR_FORM_PLAN = 0, TVR_FORM_PLAIN = 1, TVR_FORM_SPLITK = 2, TVR_FORM_TAIL = 3,
+                     TVR_FORM_STREAMK = 4 };
+enum tvr_gemm_slicing { TVR_SLICE_MODEL = 0, TVR_SLICE_ON = 1, TVR_SLICE_OFF = 2 };
+typedef struct tvr_gemm_args {
+  int32_t fmt, exact16, epi, form, form_n, form_tile, slicing, skinny;
+  int32_t M, N, K, lda, ldw, ld0, n_split, ld1h;
+  int32_t ps1h, raw_rows, ld_raw, mirror_rows, ldr, a2_col, a_buf_rows, out_buf_rows;
+  float w_scale;
+  int32_t reserved;
+  uint64_t wps;
+  const uint16_t* A;
+  const uint16_t* a2;
+  const uint16_t* W;
+  const float* bias;
+  float* out0;
+  float* out0m;
+  uint16_t* out1h;
+  float* raw;
+  const float* resid;
+  uint32_t* range_flag;
+  const int32_t* a_rows;
+  const int32_t* out_rows;
+} tvr_gemm_args;
+int tvr_gemm_launch(tvr_model* model, const tvr_gemm_args* args, void* stream);
 
 /* Kernel timing (HIP events recorded on the launch stream around every GEMM
  * launch while enabled).  tvr_profile_read synchronises the recorded events

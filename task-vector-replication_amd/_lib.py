@@ -78,6 +78,24 @@ class CAttnSeq(ctypes.Structure):
 ACT_X2F16_IL = 0x12  # include/tvr.h TVR_ACT_X2F16_IL
 
 
+class CGemmArgs(ctypes.Structure):
+    """Mirror of ``tvr_gemm_args`` (include/tvr.h; tvr_gemm_launch, the GEMM test primitive)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in (
+        "fmt", "exact16", "epi", "form", "form_n", "form_tile", "slicing", "skinny",
+        "M", "N", "K", "lda", "ldw", "ld0", "n_split", "ld1h",
+        "ps1h", "raw_rows", "ld_raw", "mirror_rows", "ldr", "a2_col", "a_buf_rows", "out_buf_rows")] +
+                [("w_scale", ctypes.c_float), ("reserved", ctypes.c_int32), ("wps", ctypes.c_uint64)] +
+                [(n, ctypes.c_void_p) for n in (
+                    "A", "a2", "W", "bias", "out0", "out0m", "out1h", "raw", "resid", "range_flag",
+                    "a_rows", "out_rows")])
+
+
+# include/tvr.h enum tvr_gemm_epi / tvr_gemm_form / tvr_gemm_slicing
+EPI_BIAS, EPI_GELU, EPI_RESID = 0, 1, 2
+FORM_PLAN, FORM_PLAIN, FORM_SPLITK, FORM_TAIL, FORM_STREAMK = 0, 1, 2, 3, 4
+SLICE_MODEL, SLICE_ON, SLICE_OFF = 0, 1, 2
+
+
 class CKernelStats(ctypes.Structure):
     _fields_ = [("gemm_launches", ctypes.c_int64 * 3), ("gemm_flops", ctypes.c_double * 3),
                 ("gemm_ms", ctypes.c_double * 3), ("gemm_bytes", ctypes.c_double * 3)]
@@ -170,6 +188,7 @@ SIGNATURES = {
                                              ctypes.c_void_p]),
     "tvr_trace_capture_pattern": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, ctypes.c_int32, c_f32p,
                                                  ctypes.c_int32, c_f32p, ctypes.c_void_p]),
+    "tvr_gemm_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CGemmArgs), ctypes.c_void_p]),
 }
 
 OPS_PATH = LIB_PATH.parent / OPS_NAME

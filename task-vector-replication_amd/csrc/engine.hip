@@ -110,6 +110,14 @@ struct PpPlan {
   int sk_base = -1;  // >= 0: tiles [0, sk_base) plain, the rest stream-K over sk_blocks blocks
   int sk_blocks = 0;
 };
+// A caller's launch form for one launch_gemm (tvr_gemm_launch, the test primitive): the plan instead of
+// plan_pp_cached's, and the sliced accumulation on (1) or off (2) instead of the model's rule (0).  The caller
+// has checked the plan against the shape (vector epilogue, S and G in range, the workspace cap).
+struct GemmForce {
+  bool plan_set = false;
+  PpPlan plan;
+  int slicing = 0;
+};
 }  // namespace
 
 struct tvr_model {
@@ -731,7 +739,7 @@ PpPlan plan_pp_cached(tvr_model* m, int M, int N, int K, int a_fmt, int epi, boo
 // in the whole-K LDS epilogue).
 int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int ldw, int M, int N,
                 int K, const GemmEpi& ep, hipStream_t st, tvr_model* m = nullptr,
-                unsigned* range_flag = nullptr) {
+                unsigned* range_flag = nullptr, const GemmForce* force = nullptr) {
   if (M <= 0 || N <= 0) return TVR_OK;
   // ACT_X2F16I: x2f16 values, A's addresses interleaved (ail); the kernels' FMT stays ACT_X2F16.  The one-plane
   // GEMM takes every epilogue and plan, two weight planes the plain EPI_BIAS launch only (no model, no plan).
@@ -776,8 +784,10 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
     // (one-plane weights, A/B of the precision it costs: TVR_WX_SLICE=0 runs them unsliced, 2 slices the
     // O + MLP-out launches only)
     static const int wx_slice = env_int("TVR_WX_SLICE", 1);
-    const bool sl = a_fmt == ACT_X2F16 && (K >= PP_SLICE_MIN_K || (m && m->K2 >= PP_SLICE_MIN_K)) &&
-                    (!W.x16 || wx_slice == 1 || (wx_slice == 2 && epi == EPI_RESID));
+    const bool sl = force && force->slicing
+                        ? a_fmt == ACT_X2F16 && force->slicing == 1
+                        : a_fmt == ACT_X2F16 && (K >= PP_SLICE_MIN_K || (m && m->K2 >= PP_SLICE_MIN_K)) &&
+                              (!W.x16 || wx_slice == 1 || (wx_slice == 2 && epi == EPI_RESID));
     if (ep.skinny && epi == EPI_BIAS && M <= SK_USE_M && !ep.out_rows && ep.k_split <= 1 && vec &&
         a_fmt != ACT_F16 && !W.x16 && !ep.a2 && !ail) {
       // a few rows (the linearised entry's G on a rank of a head split): gemm_skinny.hpp
@@ -797,7 +807,10 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
 #undef TVR_SK
     } else {
       PpPlan plan;
-      if (m && vec && epi != EPI_STATS) plan = plan_pp_cached(m, M, N, K, a_fmt, epi, a_fmt == ACT_X2F16 && W.x16);
+      if (force && force->plan_set)
+        plan = force->plan;
+      else if (m && vec && epi != EPI_STATS)
+        plan = plan_pp_cached(m, M, N, K, a_fmt, epi, a_fmt == ACT_X2F16 && W.x16);
       if (plan.sk_base >= 0) {
         if (plan.sk_base > 0)
           launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, plan.sk_base, true, sl, st, ail);
@@ -2800,6 +2813,170 @@ int tvr_gemm_planar(int32_t fmt, const uint16_t* A, int32_t lda, const uint16_t*
   return launch_gemm(EPI_BIAS, A, lda,
                      fmt == TVR_GEMM_X2F16 ? ACT_X2F16 : fmt == TVR_ACT_X2F16_IL ? ACT_X2F16I : ACT_BF16,
                      MatW{nullptr, nullptr, W, wps, w_scale}, ldw, M, N, K, e, (hipStream_t)stream);
+}
+
+int tvr_gemm_launch(tvr_model* m, const tvr_gemm_args* a, void* stream) {
+  // every check on the host, before any device call and before the model is read
+  auto bad = [](const std::string& what) { return fail(TVR_ERR_INVALID, "tvr_gemm_launch: " + what); };
+  if (!m) return bad("null model");
+  if (!a) return bad("null args");
+  if (a->fmt != TVR_GEMM_X2F16 && a->fmt != TVR_ACT_X2F16_IL && a->fmt != TVR_GEMM_BF16)
+    return bad("unknown fmt " + std::to_string(a->fmt));
+  if (a->exact16 != 0 && a->exact16 != 1) return bad("exact16 must be 0 or 1");
+  if (a->epi != TVR_EPI_BIAS && a->epi != TVR_EPI_GELU && a->epi != TVR_EPI_RESID)
+    return bad("unknown epi " + std::to_string(a->epi));
+  if (a->form < TVR_FORM_PLAN || a->form > TVR_FORM_STREAMK) return bad("unknown form " + std::to_string(a->form));
+  if (a->slicing < TVR_SLICE_MODEL || a->slicing > TVR_SLICE_OFF)
+    return bad("unknown slicing " + std::to_string(a->slicing));
+  if (a->skinny != 0 && a->skinny != 1) return bad("skinny must be 0 or 1");
+  const bool x2 = a->fmt != TVR_GEMM_BF16, il = a->fmt == TVR_ACT_X2F16_IL, x16 = a->exact16 != 0;
+  if (x16 && !x2) return bad("one exact fp16 weight plane takes an x2f16 activation format");
+  const int M = a->M, N = a->N, K = a->K, ktile = x2 ? 32 : 64;
+  if (M <= 0 || N <= 0 || K <= 0) return bad("M, N and K must be positive");
+  if (K % ktile != 0) return bad("K must be a multiple of the k-tile (" + std::to_string(ktile) + ")");
+  if (!a->A || !a->W || !a->out0) return bad("null A, W or out0");
+  if (!(a->w_scale > 0.0f) || !std::isfinite(a->w_scale)) return bad("w_scale must be positive and finite");
+  if (a->lda < K || a->lda % (il ? 32 : 8) != 0)
+    return bad("lda must be at least K and a multiple of 8 (32 in the interleaved layout)");
+  if (a->ldw < K || a->ldw % 8 != 0) return bad("ldw must be at least K and a multiple of 8");
+  const bool two_w = x2 && !x16;
+  if (two_w && (a->wps % 8 != 0 || a->wps < (uint64_t)a->ldw * (N - 1) + K))
+    return bad("wps must hold N rows of ldw and be a multiple of 8");
+  if (a->ld0 < N) return bad("ld0 must be at least N");
+  if (((uintptr_t)a->A | (uintptr_t)a->a2 | (uintptr_t)a->W | (uintptr_t)a->out0 | (uintptr_t)a->out0m |
+       (uintptr_t)a->out1h | (uintptr_t)a->raw | (uintptr_t)a->resid) & 15)
+    return bad("A, a2, W, out0, out0m, out1h, raw and resid must be 16-byte aligned");
+  if (((uintptr_t)a->bias | (uintptr_t)a->range_flag) & 3) return bad("bias and range_flag must be 4-byte aligned");
+  // rows of the output buffers (out0, out0m, out1h, raw, resid) and of the gather source
+  if (a->out_rows && a->out_buf_rows < M) return bad("out_buf_rows must be at least M under out_rows");
+  const int orows = a->out_rows ? a->out_buf_rows : M;
+  if (a->out_rows) {
+    std::vector<char> seen(orows, 0);
+    for (int r = 0; r < M; ++r) {
+      const int32_t o = a->out_rows[r];
+      if (o < 0 || o >= orows) return bad("out_rows[" + std::to_string(r) + "] outside [0, out_buf_rows)");
+      if (seen[o]) return bad("out_rows names row " + std::to_string(o) + " twice");
+      seen[o] = 1;
+    }
+  }
+  if (a->a_rows) {
+    if (a->a_buf_rows <= 0) return bad("a_buf_rows must be positive under a_rows");
+    for (int r = 0; r < M; ++r)
+      if (a->a_rows[r] < 0 || a->a_rows[r] >= a->a_buf_rows)
+        return bad("a_rows[" + std::to_string(r) + "] outside [0, a_buf_rows)");
+  }
+  if (a->a2 && (a->a2_col < 0 || a->a2_col % 256 != 0)) return bad("a2_col must be a non-negative multiple of 256");
+  int mask = N | a->ld0;
+  if (a->epi == TVR_EPI_RESID) {
+    if (!a->resid) return bad("the residual epilogue needs resid");
+    if (a->ldr < N) return bad("ldr must be at least N");
+    if (a->out0m) return bad("the residual epilogue has no mirror (out0m)");
+    mask |= a->ldr;
+  }
+  if (a->out0m && (a->mirror_rows < 0 || a->mirror_rows > orows)) return bad("mirror_rows outside [0, output rows]");
+  if (a->epi == TVR_EPI_GELU) {
+    if (a->n_split < 0 || a->n_split > N) return bad("n_split outside [0, N]");
+    const int ng = N - a->n_split;
+    if (ng > 0 && !a->out1h) return bad("the GELU epilogue needs out1h");
+    if (il ? a->ld1h < 64 * ((ng + 31) / 32)
+           : (x2 ? a->ps1h < ng || a->ld1h < a->ps1h + ng : a->ld1h < ng) || a->ps1h < 0)
+      return bad("ld1h / ps1h too small for the GELU columns");
+    mask |= a->ld1h | a->ps1h | a->n_split;
+    // the 8-column GELU stores of a whole tile are 16-byte stores of halves
+    if ((mask & 3) == 0 && ((a->ld1h | a->ps1h | a->n_split) & 7) != 0)
+      return bad("with the vector epilogue ld1h, ps1h and n_split must be multiples of 8");
+    if (a->raw) {
+      if (a->out_rows) return bad("raw is addressed by launch row: not with out_rows");
+      if (a->raw_rows < 0 || a->raw_rows > M) return bad("raw_rows outside [0, M]");
+      if (a->ld_raw < ng || ((mask & 3) == 0 && a->ld_raw % 4 != 0))
+        return bad("ld_raw must hold the GELU columns (a multiple of 4 with the vector epilogue)");
+    }
+  }
+  const bool vec = (mask & 3) == 0;
+  const bool forced = a->form >= TVR_FORM_SPLITK;
+  if (il && !x16 && (a->epi != TVR_EPI_BIAS || forced || a->skinny || a->a2))
+    return bad("the interleaved layout with two weight planes runs the plain bias launch only");
+  if (a->skinny && (forced || a->out0m || a->epi != TVR_EPI_BIAS))
+    return bad("skinny is an opt-in of plain bias launches without a mirror");
+  const int tiles = gemm_pingpong_grid(M, N), nkt = K / ktile;
+  GemmForce force;
+  force.slicing = a->slicing;
+  if (a->form != TVR_FORM_PLAN) force.plan_set = true;  // TVR_FORM_PLAIN: the default PpPlan
+  if (forced) {
+    if (!vec) return bad("a split or stream-K launch needs the vector epilogue (N and the strides multiples of 4)");
+    if (a->form == TVR_FORM_STREAMK) {
+      if (a->form_tile < 0 || a->form_tile >= tiles) return bad("form_tile outside the raster");
+      const int cnt = tiles - a->form_tile;
+      if (a->form_n < cnt || a->form_n > 256 || (long long)a->form_n > (long long)cnt * nkt)
+        return bad("stream-K blocks outside [tiles, min(256, tiles x k-tiles)]");
+      force.plan.sk_base = a->form_tile;
+      force.plan.sk_blocks = a->form_n;
+    } else {
+      const bool tail = a->form == TVR_FORM_TAIL;
+      if (tail && (a->form_tile < 1 || a->form_tile >= tiles)) return bad("form_tile outside the raster");
+      const int cnt = tail ? tiles - a->form_tile : tiles, S = a->form_n;
+      if (S < 2 || nkt / S < 8) return bad("split S must be at least 2 with at least 8 k-tiles per part");
+      if ((long long)cnt * S > 4096) return bad("more partial tiles than the workspace cap (4096)");
+      if (tail) {
+        force.plan.tail_base = a->form_tile;
+        force.plan.tail_split = S;
+      } else {
+        force.plan.ksplit = S;
+      }
+    }
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  GemmEpi e{};
+  e.bias = a->bias;
+  e.out0 = a->out0;
+  e.ld0 = a->ld0;
+  e.n_split = a->n_split;
+  e.resid = a->resid;
+  e.ldr = a->ldr;
+  e.out1h = a->out1h;
+  e.ld1h = a->ld1h;
+  e.ps1h = a->ps1h;
+  e.range_flag = a->range_flag;
+  if (a->epi == TVR_EPI_GELU) {
+    e.raw = a->raw;
+    e.raw_rows = a->raw_rows;
+    e.ld_raw = a->ld_raw;
+  }
+  e.out0m = a->out0m;
+  e.mirror_rows = a->mirror_rows;
+  e.a2 = a->a2;
+  e.a2_col = a->a2_col;
+  e.skinny = a->skinny;
+  // the row indices are host arrays (checked above): one temporary device buffer for both
+  int32_t* d_rows = nullptr;
+  int rc = TVR_OK;
+  if (a->a_rows || a->out_rows) {
+    if (hipMalloc(&d_rows, (size_t)2 * M * sizeof(int32_t)) != hipSuccess)
+      return fail(TVR_ERR_NOMEM, "tvr_gemm_launch: row index buffer");
+    hipError_t err = hipSuccess;
+    if (a->a_rows) err = hipMemcpyAsync(d_rows, a->a_rows, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (err == hipSuccess && a->out_rows)
+      err = hipMemcpyAsync(d_rows + M, a->out_rows, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // pageable host memory
+    if (err != hipSuccess) rc = fail(TVR_ERR_HIP, std::string("tvr_gemm_launch: ") + hipGetErrorString(err));
+    if (a->a_rows) e.a_rows = d_rows;
+    if (a->out_rows) e.out_rows = d_rows + M;
+  }
+  if (rc == TVR_OK) {
+    const int epi = a->epi == TVR_EPI_BIAS ? EPI_BIAS : a->epi == TVR_EPI_GELU ? EPI_SPLIT_GELU_ACT : EPI_RESID;
+    const int afmt = il ? ACT_X2F16I : x2 ? ACT_X2F16 : ACT_BF16;
+    MatW W{nullptr, nullptr, a->W, (size_t)a->wps, x2 ? a->w_scale : 1.0f, x16};
+    // (two weight planes in the interleaved layout: launch_gemm takes them without a model only)
+    rc = launch_gemm(epi, a->A, a->lda, afmt, W, a->ldw, M, N, K, e, st, il && !x16 ? nullptr : m, nullptr, &force);
+    if (rc == TVR_OK) {
+      const hipError_t err = hipGetLastError();
+      if (err != hipSuccess) rc = fail(TVR_ERR_HIP, std::string("tvr_gemm_launch: ") + hipGetErrorString(err));
+    }
+  }
+  const hipError_t err = hipStreamSynchronize(st);
+  if (rc == TVR_OK && err != hipSuccess) rc = fail(TVR_ERR_HIP, std::string("tvr_gemm_launch: ") + hipGetErrorString(err));
+  if (d_rows) (void)hipFree(d_rows);
+  return rc;
 }
 
 int tvr_lnpre_f32(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t rows, int32_t d, float eps,
