@@ -287,6 +287,41 @@ int tvr_trace_capture_resid(tvr_trace* trace, const int32_t* pos, const int32_t*
 int tvr_trace_capture_pattern(tvr_trace* trace, const int32_t* pos, const int32_t* cls, int32_t n_classes,
                               float* out_pattern, int32_t ld, float* out_mass, void* stream);
 
+/* Direct logit attribution at one query position per traced sequence, every layer and head from one clean
+ * trace (TransformerLens: cache.stack_head_results / accumulated_resid, apply_ln_to_stack, logit_attrs).
+ *   q        = pos ? pos[s] : seq_len[s] - 1
+ *   x_l      = blocks.{l}.hook_resid_pre[q] of sequence s, x_L the final residual
+ *   sigma_s  = sqrt(mean((x_L - mean x_L)^2) + ln_eps)
+ *   u_s      = W_U'[:, target[s]] - W_U'[:, contrast[s]] (contrast NULL: W_U'[:, target[s]]), W_U' the processed
+ *              w_unembed_t
+ *   out_resid[s][l]   = (x_l - mean x_l) . u_s / sigma_s      device [n_seq][L + 1] or NULL; row 0 is the
+ *              embedding's share, row L equals logit[target] - logit[contrast] minus the same difference of
+ *              b_unembed
+ *   out_head[s][l][h] = (z_l[q][h] @ W_O[l][h]) . u_s / sigma_s   device [n_seq][L][H] or NULL
+ * pos, target, contrast: host [n_seq].  The row mean is always subtracted (a trace filled on the exact-fp16
+ * path carries one constant per row, and u is mean-free only in exact arithmetic), computed as
+ * tvr_trace_read's centred export computes it.  W_O is the processed fp32 tvr_layer_weights.w2 columns
+ * [0, d) on every GEMM path.  Both outputs are written element-wise (float alignment).  Sums run in a fixed
+ * order, no atomics: out_head[s][l][h] depends bit for bit only on sequence s' rows, l and h, not on n_seq.
+ * Runs a pending deferred clean forward first; everything is enqueued on `stream`.  Timed under
+ * TVR_HBM_CAPTURE (two spans: the direction pass, the head pass).  All arguments are validated before any
+ * device call: TVR_ERR_INVALID for a null trace or target, both outputs null, an empty trace, a pos outside
+ * its sequence, a target or contrast outside [0, d_vocab).  (Backward-compatible addition: ABI 11.) */
+int tvr_trace_logit_attribution(tvr_trace* trace, const int32_t* pos, const int32_t* target,
+                                const int32_t* contrast, float* out_head, float* out_resid, void* stream);
+/* Logit lens: every layer's residual row at the query position through the final LayerNormPre and the
+ * unembedding, out index [s][l], l in [0, L] (l == L: the model's own last-layer distribution at q).
+ * Row l of sequence s is gathered from the trace in place.  targets host [n_seq] or NULL; out_prob device
+ * [n_seq][L + 1] = softmax(logits)[targets[s]] or NULL (needs targets); out_topk device [n_seq][L + 1][topk]
+ * int32 (descending, lowest id on ties) or NULL; topk in [1, 16] with out_topk (else ignored, in [0, 16]).
+ * The rows take tvr_forward_clean's final stage as it is: LNPre with each row's own scale, the unembed with
+ * the fused statistics on the model's GEMM path (the exact-fp16 unembed where bound).  Runs a pending
+ * deferred clean forward first.  TVR_ERR_INVALID for a null or empty trace, no output at all, out_prob
+ * without targets, a bad topk, a pos outside its sequence, a target outside [0, d_vocab); validated before
+ * any device call.  (Backward-compatible addition: ABI 11.) */
+int tvr_trace_logit_lens(tvr_trace* trace, const int32_t* pos, const int32_t* targets, float* out_prob,
+                         int32_t* out_topk, int32_t topk, void* stream);
+
 /* Batched clean forward of n_seq prompts (ragged lengths, packed tokens).
  * Replaces the per-prompt model.forward / run_with_cache calls
  * (scratch2.py:96,143,183,297; scratch.py:127,132,137).
@@ -500,6 +535,24 @@ int tvr_attention_pattern(tvr_model* model, const float* qkv, int32_t rows, cons
                           const int32_t* qpos, int32_t n_seq, const int32_t* cls, int32_t n_classes,
                           float* out_pattern, int32_t ld, float* out_mass, const float* cos_t,
                           const float* sin_t, void* stream);
+/* The head pass of tvr_trace_logit_attribution alone, on a caller's buffers (one layer): which heads write
+ * along a direction.
+ *   out[i][h] = (z[i][h*dh .. (h+1)*dh) @ W_O[layer][h]) . dirs[i]      i in [0, n)
+ * z, dirs device [n][d], 16-byte aligned (else TVR_ERR_INVALID); out device [n][H], written element-wise
+ * (float alignment); nothing outside [n][H] is written and no row beyond n is read.  W_O: the processed fp32
+ * tvr_layer_weights.w2 columns [0, d), the operand of tvr_project_heads, on every GEMM path and with
+ * exact-fp16 weights bound.  The bits of out[i][h] depend only on row i, the layer and the head.
+ * TVR_ERR_INVALID for null arguments, n <= 0 or a layer out of range, before any device call.  Enqueues on
+ * `stream` without synchronising.  (Backward-compatible addition: ABI 11.) */
+int tvr_head_attribution(tvr_model* model, int32_t layer, const float* z, const float* dirs, int32_t n,
+                         float* out, void* stream);
+/* Vocabulary decoding of any rows (task vectors, function vectors, residual rows): tvr_trace_logit_lens'
+ * stage on a caller's buffer.  rows device [n][d], 16-byte aligned; targets host [n] or NULL; out_prob
+ * device [n] or NULL; out_topk device [n][topk] or NULL; same rules and errors as tvr_trace_logit_lens, and
+ * TVR_ERR_INVALID for a null model or rows, n <= 0 or rows not 16-byte aligned.
+ * (Backward-compatible addition: ABI 11.) */
+int tvr_decode_rows(tvr_model* model, const float* rows, int32_t n, const int32_t* targets, float* out_prob,
+                    int32_t* out_topk, int32_t topk, void* stream);
 /* One planar GEMM through the engine's own dispatch (launch_gemm: the skinny
  * kernel, gemm_pingpong_kernel plain, split over K, with a split tail or
  * stream-K and their reduce kernels), C = A W^T under one fused epilogue.  The
@@ -611,7 +664,9 @@ enum tvr_hbm_kind {
                            * patches of tvr_patch_sweep_sets, one launch per patched layer: z slices zeroed +
                            * residual rows read and written + vectors read */
   TVR_HBM_CAPTURE = 1,    /* extraction: sum of hook_z at every prompt's last row -> [d] per layer; and
-                           * tvr_trace_capture_resid: rows read x (L + 1) x d x 4 + out read and written */
+                           * tvr_trace_capture_resid: rows read x (L + 1) x d x 4 + out read and written; and
+                           * tvr_trace_logit_attribution / tvr_head_attribution: the direction pass's rows, and per
+                           * layer of the head pass W_O once per chunk of 16 sequences + the z and direction rows */
   TVR_HBM_LNPRE = 2,      /* LayerNormPre rows -> GEMM input format */
   TVR_HBM_ATTENTION = 3,  /* attention: fp32 Q/K/V rows in, z out (activation format [+ fp32 hook_z]); and
                            * tvr_trace_capture_pattern: per layer the Q row + the K rows read, pattern / mass written */

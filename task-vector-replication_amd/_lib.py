@@ -189,6 +189,14 @@ SIGNATURES = {
     "tvr_trace_capture_pattern": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, ctypes.c_int32, c_f32p,
                                                  ctypes.c_int32, c_f32p, ctypes.c_void_p]),
     "tvr_gemm_launch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CGemmArgs), ctypes.c_void_p]),
+    "tvr_head_attribution": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_int32, c_f32p,
+                                            ctypes.c_void_p]),
+    "tvr_trace_logit_attribution": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p,
+                                                   ctypes.c_void_p]),
+    "tvr_decode_rows": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int32, c_i32p, c_f32p, c_i32p,
+                                       ctypes.c_int32, ctypes.c_void_p]),
+    "tvr_trace_logit_lens": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_f32p, c_i32p, ctypes.c_int32,
+                                            ctypes.c_void_p]),
 }
 
 OPS_PATH = LIB_PATH.parent / OPS_NAME
@@ -202,6 +210,11 @@ RESID_OPS = ("capture_resid",)
 PATTERN_OPS = ("capture_pattern",)
 # tvr_trace_capture_pattern's upper limit on n_classes (include/tvr.h)
 PATTERN_MAX_CLASSES = 64
+# direct logit attribution and the logit lens / vocabulary decoding (tvr_head_attribution,
+# tvr_trace_logit_attribution, tvr_trace_logit_lens, tvr_decode_rows)
+ATTRIBUTION_OPS = ("head_attribution", "logit_attribution", "logit_lens", "decode_rows")
+# the largest top-k of the row statistics (csrc/kernels.hpp STATS_MAX_K)
+STATS_MAX_K = 16
 
 _LIB = None
 _OPS_LOADED = False

@@ -26,6 +26,7 @@
 #include "gemm_f32.hpp"
 #include "attention_mfma.hpp"
 #include "attention_pattern.hpp"
+#include "logit_attribution.hpp"
 #include "gemm_pingpong.hpp"
 #include "gemm_skinny.hpp"
 #include "gemm_planar.hpp"
@@ -1221,6 +1222,31 @@ int check_pattern_args(const char* fn, const int32_t* cls, int n_cls, int32_t n_
   return TVR_OK;
 }
 
+// head_attribution_kernel over n_layers layers from layer0 (logit_attribution.hpp): grid (chunks of 16 rows, H,
+// layers).  z rows: slab lz at z + lz * z_lstride, row d_zrows[i] (null: i).  out[(i * n_layers + lz) * H + h].
+// Timed under TVR_HBM_CAPTURE: per layer W_O as each chunk of 16 rows reads it, the z and direction rows, out.
+int launch_head_attribution(tvr_model* m, const char* fn, const float* dirs, int n, const float* z, size_t z_lstride,
+                            const int32_t* d_zrows, int layer0, int n_layers, float* out, hipStream_t st) {
+  const tvr_config& c = m->cfg;
+  const int d = c.d_model, dh = c.d_head, H = c.n_heads;
+  const int chunks = (n + ATTR_CHUNK - 1) / ATTR_CHUNK;
+  if (!(dh == 16 || dh == 64 || dh == 80 || dh == 128) || d % 16 != 0)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": the attribution kernel covers d_head 16 / 64 / 80 / 128");
+  if (H > 65535 || n_layers > 65535)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": too many heads or layers for one launch");
+  ProfSpan ps(m, st);
+  const dim3 grid((unsigned)chunks, (unsigned)H, (unsigned)n_layers), block(64 * ATTR_WAVES);
+#define TVR_ATTR(NT)                                                                                              \
+  hipLaunchKernelGGL((head_attribution_kernel<NT>), grid, block, 0, st, dirs, n, z, z_lstride, d_zrows, m->d_w2s, \
+                     layer0, m->K2, out, n_layers, H, d)
+  if (dh == 16) { TVR_ATTR(1); } else if (dh == 64) { TVR_ATTR(4); }
+  else if (dh == 80) { TVR_ATTR(5); } else { TVR_ATTR(8); }
+#undef TVR_ATTR
+  TVR_HIP(hipGetLastError());
+  ps.done(TVR_HBM_CAPTURE, 4.0 * n_layers * ((double)chunks * d * d + 2.0 * n * d + (double)n * H));
+  return TVR_OK;
+}
+
 // One transformer block over the first R rows (Pythia parallel residual):
 //   x = LNPre(resid); [qkv | h] = x @ W1^T + b1; z = attn(qkv); resid += [z|gelu h] @ W2^T + b2
 // (run_block computes up to z; run_block_out the second projection.)
@@ -2078,6 +2104,171 @@ int tvr_trace_capture_pattern(tvr_trace* t, const int32_t* pos, const int32_t* c
   ps.done(TVR_HBM_ATTENTION, 4.0 * L * ((n_seq + keys) * d + (double)n_seq * H * ((out_pattern ? ld : 0) +
                                                                                    (out_mass ? n_classes : 0))));
   return TVR_OK;
+}
+
+int tvr_head_attribution(tvr_model* m, int32_t layer, const float* z, const float* dirs, int32_t n, float* out,
+                         void* stream) {
+  const char* fn = "tvr_head_attribution";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!m) return bad("null model");
+  if (!z || !dirs || !out) return bad("null argument");
+  if (n <= 0) return bad("n must be positive");
+  if (layer < 0 || layer >= m->cfg.n_layers) return bad("layer out of range");
+  if (((uintptr_t)z & 15) || ((uintptr_t)dirs & 15)) return bad("z and dirs must be 16-byte aligned");
+  return launch_head_attribution(m, fn, dirs, n, z, 0, nullptr, layer, 1, out, (hipStream_t)stream);
+}
+
+int tvr_trace_logit_attribution(tvr_trace* t, const int32_t* pos, const int32_t* target, const int32_t* contrast,
+                                float* out_head, float* out_resid, void* stream) {
+  const char* fn = "tvr_trace_logit_attribution";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!t) return bad("null trace");
+  if (!target) return bad("null target");
+  if (!out_head && !out_resid) return bad("out_head and out_resid are both null");
+  if (t->n_seq <= 0) return bad("trace is empty: run tvr_forward_clean first");
+  tvr_model* m = t->model;
+  const tvr_config& c = m->cfg;
+  const int L = c.n_layers, d = c.d_model, n_seq = t->n_seq;
+  std::vector<int32_t> rows(n_seq), tg(target, target + n_seq), ct;
+  if (contrast) ct.assign(contrast, contrast + n_seq);
+  for (int s = 0; s < n_seq; ++s) {
+    const int q = pos ? pos[s] : t->seq_len[s] - 1;
+    if (q < 0 || q >= t->seq_len[s]) return bad("pos of sequence " + std::to_string(s) + " out of range");
+    if (tg[s] < 0 || tg[s] >= c.d_vocab) return bad("target of sequence " + std::to_string(s) + " outside [0, d_vocab)");
+    if (contrast && (ct[s] < 0 || ct[s] >= c.d_vocab))
+      return bad("contrast of sequence " + std::to_string(s) + " outside [0, d_vocab)");
+    rows[s] = t->seq_off[s] + q;
+  }
+  if (L + 1 > 65535) return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": too many layers for one launch");
+  // the direction-pass kernels read whole float4s of the trace, workspace and w_unembed_t rows
+  if (d % 4 != 0 || ((uintptr_t)m->w_unembed_t & 15))
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": d_model must be a multiple of 4 and w_unembed_t 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  TVR_TRY(flush_pending(t, stream));  // a deferred clean forward runs now (it uses the workspace: carve after it)
+  Carve cv;
+  const size_t o_rows = cv.take<int32_t>(n_seq);
+  const size_t o_tg = cv.take<int32_t>(n_seq);
+  const size_t o_ct = contrast ? cv.take<int32_t>(n_seq) : 0;
+  const size_t o_dirs = cv.take<float>((size_t)n_seq * d);
+  TVR_TRY(ensure_workspace(m, cv.off, st));
+  char* base = m->ws;
+  UploadBatch ub;
+  ub.add(o_rows, rows);
+  ub.add(o_tg, tg);
+  if (contrast) ub.add(o_ct, ct);
+  TVR_TRY(flush_uploads(m, st, base, ub));
+  const size_t lstride = (size_t)t->max_tokens * d;
+  const int32_t* d_rows = (const int32_t*)(base + o_rows);
+  float* dirs = (float*)(base + o_dirs);
+  {
+    ProfSpan ps(m, st);
+    hipLaunchKernelGGL(attr_direction_kernel, dim3((unsigned)n_seq), dim3(64), 0, st, t->resid + L * lstride, d_rows,
+                       m->w_unembed_t, (const int32_t*)(base + o_tg),
+                       contrast ? (const int32_t*)(base + o_ct) : nullptr, c.ln_eps, dirs, d);
+    TVR_HIP(hipGetLastError());
+    if (out_resid) {
+      hipLaunchKernelGGL(attr_resid_kernel, dim3((unsigned)n_seq, (unsigned)(L + 1)), dim3(64), 0, st, t->resid,
+                         lstride, d_rows, dirs, out_resid, L + 1, d);
+      TVR_HIP(hipGetLastError());
+    }
+    // the final rows and the unembed rows in, the directions out; then every layer's row and the direction in
+    ps.done(TVR_HBM_CAPTURE, 4.0 * n_seq * d * ((contrast ? 4.0 : 3.0) + (out_resid ? 2.0 * (L + 1) : 0.0)));
+  }
+  if (out_head) TVR_TRY(launch_head_attribution(m, fn, dirs, n_seq, t->z, lstride, d_rows, 0, L, out_head, st));
+  return TVR_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// LNPre + unembed + statistics (run_final) of n rows of `x` (rows of d floats; row idx_in[i], or i when idx_in
+// is empty): the workspace is carved as forward_impl carves its final stage.  targets: host [n] or null.
+// run_final walks its rows in chunks through the index array (d_rows + s), so dense rows get an identity
+// index, as forward_impl's all_rows path builds one: a null index is right for the first chunk only.
+int decode_impl(tvr_model* m, const float* x, const std::vector<int32_t>& idx_in, int n, const int32_t* targets,
+                float* out_prob, int32_t* out_topk, int topk, hipStream_t st) {
+  const int d = m->cfg.d_model, fmt = act_fmt(m);
+  std::vector<int32_t> idx(idx_in);
+  if (idx.empty()) {
+    idx.resize(n);
+    for (int i = 0; i < n; ++i) idx[i] = i;
+  }
+  std::vector<int32_t> tg(n, -1);
+  if (targets) std::copy(targets, targets + n, tg.begin());
+  const int FC = std::min(final_chunk(m, fmt, nullptr), n);
+  Carve cv;
+  const size_t o_idx = cv.take<int32_t>(n);
+  const size_t o_tg = cv.take<int32_t>(n);
+  const size_t o_xf = cv.take<float>((size_t)FC * d);
+  const size_t o_lg = cv.take<float>(final_scratch_floats(m, fmt, FC, topk, nullptr));
+  TVR_TRY(ensure_workspace(m, cv.off, st));
+  char* base = m->ws;
+  UploadBatch ub;
+  ub.add(o_idx, idx);
+  ub.add(o_tg, tg);
+  TVR_TRY(flush_uploads(m, st, base, ub));
+  return run_final(m, x, (const int32_t*)(base + o_idx), (const int32_t*)(base + o_tg), n,
+                   (float*)(base + o_xf), (float*)(base + o_lg), out_prob, out_topk, topk, nullptr, fmt, st);
+}
+
+// The output / top-k checks tvr_decode_rows and tvr_trace_logit_lens share; topk_eff: the k run_final gets.
+int check_decode_args(const char* fn, const tvr_config& c, const int32_t* targets, int n_targets,
+                      const float* out_prob, const int32_t* out_topk, int32_t topk, int& topk_eff) {
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!out_prob && !out_topk) return bad("out_prob and out_topk are both null");
+  if (out_prob && !targets) return bad("out_prob needs targets");
+  if (out_topk && (topk <= 0 || topk > STATS_MAX_K))
+    return bad("topk must be in [1, " + std::to_string(STATS_MAX_K) + "] with out_topk");
+  if (!out_topk && (topk < 0 || topk > STATS_MAX_K)) return bad("topk must be in [0, " + std::to_string(STATS_MAX_K) + "]");
+  for (int i = 0; targets && i < n_targets; ++i)
+    if (targets[i] < 0 || targets[i] >= c.d_vocab)
+      return bad("target " + std::to_string(i) + " outside [0, d_vocab)");
+  topk_eff = out_topk ? topk : 0;
+  return TVR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tvr_decode_rows(tvr_model* m, const float* rows, int32_t n, const int32_t* targets, float* out_prob,
+                    int32_t* out_topk, int32_t topk, void* stream) {
+  const char* fn = "tvr_decode_rows";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!m) return bad("null model");
+  if (!rows) return bad("null rows");
+  if (n <= 0) return bad("n must be positive");
+  if ((uintptr_t)rows & 15) return bad("rows must be 16-byte aligned");
+  int k = 0;
+  TVR_TRY(check_decode_args(fn, m->cfg, targets, n, out_prob, out_topk, topk, k));
+  return decode_impl(m, rows, {}, n, targets, out_prob, out_topk, k, (hipStream_t)stream);
+}
+
+int tvr_trace_logit_lens(tvr_trace* t, const int32_t* pos, const int32_t* targets, float* out_prob,
+                         int32_t* out_topk, int32_t topk, void* stream) {
+  const char* fn = "tvr_trace_logit_lens";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!t) return bad("null trace");
+  if (t->n_seq <= 0) return bad("trace is empty: run tvr_forward_clean first");
+  tvr_model* m = t->model;
+  const int L = m->cfg.n_layers, n_seq = t->n_seq;
+  int k = 0;
+  TVR_TRY(check_decode_args(fn, m->cfg, targets, n_seq, out_prob, out_topk, topk, k));
+  if ((int64_t)(L + 1) * t->max_tokens > INT_MAX || (int64_t)(L + 1) * n_seq > INT_MAX)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": the trace's row indices do not fit in int32");
+  // row l * max_tokens + row of the contiguous [L + 1][max_tokens][d] residual slabs: no copy
+  std::vector<int32_t> idx((size_t)n_seq * (L + 1)), tg;
+  if (targets) tg.resize(idx.size());
+  for (int s = 0; s < n_seq; ++s) {
+    const int q = pos ? pos[s] : t->seq_len[s] - 1;
+    if (q < 0 || q >= t->seq_len[s]) return bad("pos of sequence " + std::to_string(s) + " out of range");
+    for (int l = 0; l <= L; ++l) {
+      idx[(size_t)s * (L + 1) + l] = l * t->max_tokens + t->seq_off[s] + q;
+      if (targets) tg[(size_t)s * (L + 1) + l] = targets[s];
+    }
+  }
+  TVR_TRY(flush_pending(t, stream));  // a deferred clean forward runs now (it uses the workspace: carve after it)
+  return decode_impl(m, t->resid, idx, (int)idx.size(), targets ? tg.data() : nullptr, out_prob, out_topk, k,
+                     (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,10 @@
 //   tvr::forward_logits  tvr_forward_logits              (scratch.py:143,206,209)
 //   tvr::capture_resid   tvr_trace_capture_resid         (run_with_cache + hook_resid_pre[l][0, pos], summed)
 //   tvr::capture_pattern tvr_trace_capture_pattern       (run_with_cache + cache["pattern", l][0, :, pos, :])
+//   tvr::head_attribution tvr_head_attribution           (einsum of z, W_O and a direction per head)
+//   tvr::logit_attribution tvr_trace_logit_attribution   (stack_head_results / accumulated_resid + logit_attrs)
+//   tvr::logit_lens      tvr_trace_logit_lens            (ln_final + unembed of every layer's resid_pre row)
+//   tvr::decode_rows     tvr_decode_rows                 (ln_final + unembed of any vectors)
 //
 // Every op enqueues on torch's CURRENT stream of the output device and
 // allocates its outputs through torch's caching allocator; host arrays
@@ -256,6 +260,105 @@ void capture_pattern(int64_t trace, const std::optional<at::Tensor>& pos, const 
         "tvr_trace_capture_pattern");
 }
 
+bool dev_tensor(const at::Tensor& t, const c10::Device& dev, at::ScalarType ty) {
+  return t.device() == dev && t.scalar_type() == ty && t.is_contiguous();
+}
+
+// out [n, H] = per-head attribution of z [n, d] along dirs [n, d] at one layer (tvr_head_attribution).  z and
+// dirs: contiguous fp32 device tensors whose storage is 16-byte aligned (the engine refuses others); out: a
+// contiguous fp32 device tensor, an offset view is fine.  d_model / n_heads: the model's, which the widths must equal.
+void head_attribution(int64_t model, int64_t layer, const at::Tensor& z, const at::Tensor& dirs, int64_t d_model,
+                      int64_t n_heads, at::Tensor& out) {
+  const c10::Device dev = out.device();
+  need_gpu(dev);
+  TORCH_CHECK_VALUE(z.dim() == 2 && z.size(0) > 0 && z.size(1) == d_model && dev_tensor(z, dev, at::kFloat) &&
+                        dirs.sizes() == z.sizes() && dev_tensor(dirs, dev, at::kFloat),
+                    "tvr: z and dirs must be contiguous fp32 tensors [n, d_model] on the output's device");
+  TORCH_CHECK_VALUE(dev_tensor(out, dev, at::kFloat) && out.dim() == 2 && out.size(0) == z.size(0) &&
+                        out.size(1) == n_heads,
+                    "tvr: out must be a contiguous fp32 tensor [n, n_heads]");
+  DeviceGuard guard(dev);
+  check(tvr_head_attribution(as_model(model), (int32_t)layer, z.data_ptr<float>(), dirs.data_ptr<float>(),
+                             (int32_t)z.size(0), out.data_ptr<float>(), cur_stream(dev)),
+        "tvr_head_attribution");
+}
+
+// Direct logit attribution of a trace (tvr_trace_logit_attribution).  pos / contrast: CPU int32 [n_seq] or None;
+// target: CPU int32 [n_seq]; out_head [n_seq, L, H] and out_resid [n_seq, L + 1]: contiguous fp32 device tensors,
+// at least one of them.
+void logit_attribution(int64_t trace, const std::optional<at::Tensor>& pos, const at::Tensor& target,
+                       const std::optional<at::Tensor>& contrast, int64_t n_seq, int64_t n_layers, int64_t n_heads,
+                       const std::optional<at::Tensor>& out_head, const std::optional<at::Tensor>& out_resid) {
+  TORCH_CHECK_VALUE(trace != 0, "tvr: logit_attribution needs a trace");
+  TORCH_CHECK_VALUE(out_head.has_value() || out_resid.has_value(), "tvr: logit_attribution needs out_head or out_resid");
+  TORCH_CHECK_VALUE(!pos.has_value() || pos->numel() == n_seq, "tvr: pos must have one entry per traced sequence");
+  TORCH_CHECK_VALUE(target.numel() == n_seq, "tvr: target must have one entry per traced sequence");
+  TORCH_CHECK_VALUE(!contrast.has_value() || contrast->numel() == n_seq,
+                    "tvr: contrast must have one entry per traced sequence");
+  const c10::Device dev = out_head.has_value() ? out_head->device() : out_resid->device();
+  need_gpu(dev);
+  TORCH_CHECK_VALUE(!out_head.has_value() || (dev_tensor(*out_head, dev, at::kFloat) && out_head->dim() == 3 &&
+                                              out_head->size(0) == n_seq && out_head->size(1) == n_layers &&
+                                              out_head->size(2) == n_heads),
+                    "tvr: out_head must be a contiguous fp32 tensor [n_seq, n_layers, n_heads]");
+  TORCH_CHECK_VALUE(!out_resid.has_value() || (dev_tensor(*out_resid, dev, at::kFloat) && out_resid->dim() == 2 &&
+                                               out_resid->size(0) == n_seq && out_resid->size(1) == n_layers + 1),
+                    "tvr: out_resid must be a contiguous fp32 tensor [n_seq, n_layers + 1]");
+  DeviceGuard guard(dev);
+  check(tvr_trace_logit_attribution(reinterpret_cast<tvr_trace*>(static_cast<intptr_t>(trace)),
+                                    opt_host_i32(pos, "pos"), host_i32(target, "target"),
+                                    opt_host_i32(contrast, "contrast"),
+                                    out_head.has_value() ? out_head->data_ptr<float>() : nullptr,
+                                    out_resid.has_value() ? out_resid->data_ptr<float>() : nullptr, cur_stream(dev)),
+        "tvr_trace_logit_attribution");
+}
+
+// The output pair of logit_lens / decode_rows: out_prob fp32 with `rows` elements, out_topk int32 [.., topk].
+c10::Device decode_outputs(const std::optional<at::Tensor>& targets, int64_t n_targets, int64_t rows, int64_t topk,
+                           const std::optional<at::Tensor>& out_prob, const std::optional<at::Tensor>& out_topk) {
+  TORCH_CHECK_VALUE(out_prob.has_value() || out_topk.has_value(), "tvr: needs out_prob or out_topk");
+  TORCH_CHECK_VALUE(!out_prob.has_value() || targets.has_value(), "tvr: out_prob needs targets");
+  TORCH_CHECK_VALUE(!targets.has_value() || targets->numel() == n_targets, "tvr: targets must have one entry per row");
+  const c10::Device dev = out_prob.has_value() ? out_prob->device() : out_topk->device();
+  need_gpu(dev);
+  TORCH_CHECK_VALUE(!out_prob.has_value() || (dev_tensor(*out_prob, dev, at::kFloat) && out_prob->numel() == rows),
+                    "tvr: out_prob must be a contiguous fp32 tensor with one entry per decoded row");
+  TORCH_CHECK_VALUE(!out_topk.has_value() || (topk > 0 && dev_tensor(*out_topk, dev, at::kInt) &&
+                                              out_topk->numel() == rows * topk && out_topk->size(-1) == topk),
+                    "tvr: out_topk must be a contiguous int32 tensor [rows, topk] with topk > 0");
+  return dev;
+}
+
+// Logit lens of a trace (tvr_trace_logit_lens).  pos / targets: CPU int32 [n_seq] or None; out_prob
+// [n_seq, L + 1] fp32 and out_topk [n_seq, L + 1, topk] int32: contiguous device tensors, at least one.
+void logit_lens(int64_t trace, const std::optional<at::Tensor>& pos, const std::optional<at::Tensor>& targets,
+                int64_t n_seq, int64_t n_layers, int64_t topk, const std::optional<at::Tensor>& out_prob,
+                const std::optional<at::Tensor>& out_topk) {
+  TORCH_CHECK_VALUE(trace != 0, "tvr: logit_lens needs a trace");
+  TORCH_CHECK_VALUE(!pos.has_value() || pos->numel() == n_seq, "tvr: pos must have one entry per traced sequence");
+  const c10::Device dev = decode_outputs(targets, n_seq, n_seq * (n_layers + 1), topk, out_prob, out_topk);
+  DeviceGuard guard(dev);
+  check(tvr_trace_logit_lens(reinterpret_cast<tvr_trace*>(static_cast<intptr_t>(trace)), opt_host_i32(pos, "pos"),
+                             opt_host_i32(targets, "targets"),
+                             out_prob.has_value() ? out_prob->data_ptr<float>() : nullptr,
+                             out_topk.has_value() ? out_topk->data_ptr<int32_t>() : nullptr, (int32_t)topk,
+                             cur_stream(dev)),
+        "tvr_trace_logit_lens");
+}
+
+// Vocabulary decoding of rows [n, d] (tvr_decode_rows): a contiguous fp32 device tensor, 16-byte aligned.
+void decode_rows(int64_t model, const at::Tensor& rows, const std::optional<at::Tensor>& targets, int64_t topk,
+                 int64_t d_model, const std::optional<at::Tensor>& out_prob, const std::optional<at::Tensor>& out_topk) {
+  TORCH_CHECK_VALUE(rows.dim() == 2 && rows.size(0) > 0 && rows.size(1) == d_model, "tvr: rows must be [n, d_model]");
+  const c10::Device dev = decode_outputs(targets, rows.size(0), rows.size(0), topk, out_prob, out_topk);
+  TORCH_CHECK_VALUE(dev_tensor(rows, dev, at::kFloat), "tvr: rows must be a contiguous fp32 tensor on the outputs' device");
+  DeviceGuard guard(dev);
+  check(tvr_decode_rows(as_model(model), rows.data_ptr<float>(), (int32_t)rows.size(0),
+                        opt_host_i32(targets, "targets"), out_prob.has_value() ? out_prob->data_ptr<float>() : nullptr,
+                        out_topk.has_value() ? out_topk->data_ptr<int32_t>() : nullptr, (int32_t)topk, cur_stream(dev)),
+        "tvr_decode_rows");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tvr, m) {
@@ -272,6 +375,13 @@ TORCH_LIBRARY(tvr, m) {
   m.def("capture_resid(int trace, Tensor? pos, Tensor? groups, int n_groups, int n_seq, Tensor(a!) out) -> Tensor(a!)");
   m.def("capture_pattern(int trace, Tensor? pos, Tensor? cls, int n_classes, int n_seq, int n_layers, int n_heads, "
         "Tensor(a!)? out_pattern, Tensor(b!)? out_mass) -> ()");
+  m.def("head_attribution(int model, int layer, Tensor z, Tensor dirs, int d_model, int n_heads, Tensor(a!) out) -> ()");
+  m.def("logit_attribution(int trace, Tensor? pos, Tensor target, Tensor? contrast, int n_seq, int n_layers, "
+        "int n_heads, Tensor(a!)? out_head, Tensor(b!)? out_resid) -> ()");
+  m.def("logit_lens(int trace, Tensor? pos, Tensor? targets, int n_seq, int n_layers, int topk, "
+        "Tensor(a!)? out_prob, Tensor(b!)? out_topk) -> ()");
+  m.def("decode_rows(int model, Tensor rows, Tensor? targets, int topk, int d_model, Tensor(a!)? out_prob, "
+        "Tensor(b!)? out_topk) -> ()");
 }
 
 // Mixed host / device tensor arguments: one implementation for every backend key.
@@ -283,4 +393,8 @@ TORCH_LIBRARY_IMPL(tvr, CompositeExplicitAutograd, m) {
   m.impl("forward_logits", &forward_logits);
   m.impl("capture_resid", &capture_resid);
   m.impl("capture_pattern", &capture_pattern);
+  m.impl("head_attribution", &head_attribution);
+  m.impl("logit_attribution", &logit_attribution);
+  m.impl("logit_lens", &logit_lens);
+  m.impl("decode_rows", &decode_rows);
 }

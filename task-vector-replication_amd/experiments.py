@@ -33,6 +33,14 @@ role (one pass over the trace's Q / K rows, no patched forward):
 
   head_attention_profile, top_attention_heads
 
+and the two readings of a clean trace through the unembedding: direct logit
+attribution (TransformerLens' stack_head_results + logit_attrs; the second cheap
+head signal beside the attention profile, on the CIE sweep's own inputs) and the
+logit lens / vocabulary decoding of residual rows and of task / function vectors:
+
+  head_logit_attribution, top_attribution_heads, logit_lens_by_layer,
+  decode_vectors
+
 Drop-in notes
 * ``model`` is an ``amd.Model`` instead of a HookedTransformer; it must be
   passed (the reference's defaults bind a module-global model).
@@ -46,7 +54,7 @@ Drop-in notes
 from __future__ import annotations
 
 import random
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -326,6 +334,107 @@ def top_attention_heads(profile: torch.Tensor, role, num_heads: int) -> List[Tup
         raise ValueError("num_heads must be in [1, n_layers * n_heads]")
     _, idx = torch.topk(profile[:, :, int(role)].flatten(), num_heads)
     return [(int(i) // H, int(i) % H) for i in idx.tolist()]
+
+
+# ------------------------------------------------ direct logit attribution / logit lens
+class HeadLogitAttribution(NamedTuple):
+    """Means over prompts of the direct logit attribution of the answer token at
+    the last position (``head_logit_attribution``)."""
+    heads: torch.Tensor   # [n_layers, n_heads]: each head's hook_result
+    rest: torch.Tensor    # [n_layers]: the layer's MLP and its biases (b_O + b_out are merged in the engine)
+    embed: torch.Tensor   # []: the embedding
+    total: torch.Tensor   # []: the final residual = logit[answer] (− logit[contrast]) minus b_U's share
+
+
+def _check_prompts_answers(scrambled_prompts, prompt_answers, contrast_answers=None):
+    if len(scrambled_prompts) == 0:
+        raise ValueError("no prompts")
+    if len(scrambled_prompts) != len(prompt_answers):
+        raise ValueError("Prompt answers must be of the same length as scrambled prompts")
+    if contrast_answers is not None and len(contrast_answers) != len(scrambled_prompts):
+        raise ValueError("Contrast answers must be of the same length as scrambled prompts")
+
+
+@range_checked
+def head_logit_attribution(scrambled_prompts, prompt_answers, model: Model = None,
+                           contrast_answers=None) -> HeadLogitAttribution:
+    """Direct logit attribution of each prompt's answer token (its first token,
+    as the CIE sweep scores it) at the last position, averaged over prompts:
+    how much every head, every layer's MLP and biases, and the embedding push
+    the answer's logit (or, with ``contrast_answers``, the logit difference),
+    through the final LayerNorm's scale.  Prompts and answers in the forms
+    ``calculate_average_causal_indirect_effect`` takes, so both rank the same
+    heads on the same prompts; this one needs one clean forward into a trace
+    and one pass over it (``Trace.logit_attribution``) per ``EXTRACT_BATCH``
+    prompts, no patched forward.  ``rest[l] = resid[l + 1] − resid[l] −
+    Σ_h heads[l, h]``."""
+    _check_prompts_answers(scrambled_prompts, prompt_answers, contrast_answers)
+    prompts, answers = normalize_cie_inputs(model, scrambled_prompts, prompt_answers)
+    contrast = normalize_cie_inputs(model, [], contrast_answers)[1] if contrast_answers is not None else None
+    heads = resid = None
+    for a, b in _chunks(len(prompts), EXTRACT_BATCH):
+        seqs = prompts[a:b]
+        trace = model._sweep_trace(len(seqs), sum(len(s) for s in seqs))
+        model.forward_clean(seqs, trace=trace)
+        h, r = trace.logit_attribution(answers[a:b], contrast=contrast[a:b] if contrast is not None else None)
+        h, r = h.sum(0), r.sum(0)  # prompts in order: reproducible
+        heads, resid = (h, r) if heads is None else (heads + h, resid + r)
+    heads, resid = heads / len(prompts), resid / len(prompts)
+    rest = resid[1:] - resid[:-1] - heads.sum(1)
+    return HeadLogitAttribution(heads, rest, resid[0], resid[-1])
+
+
+def top_attribution_heads(heads: torch.Tensor, num_heads: int) -> List[Tuple[int, int]]:
+    """The ``num_heads`` (layer, head) pairs with the largest attribution of a
+    ``head_logit_attribution(...).heads``, highest first (torch.topk's order and
+    tie rule, as ``top_cie_heads``)."""
+    if not isinstance(heads, torch.Tensor) or heads.dim() != 2:
+        raise ValueError("heads must be of shape (n_layers, n_heads)")
+    H = heads.shape[1]
+    if not 0 < num_heads <= heads.shape[0] * H:
+        raise ValueError("num_heads must be in [1, n_layers * n_heads]")
+    _, idx = torch.topk(heads.flatten(), num_heads)
+    return [(int(i) // H, int(i) % H) for i in idx.tolist()]
+
+
+@range_checked
+def logit_lens_by_layer(scrambled_prompts, prompt_answers, model: Model = None, topk: int = 1):
+    """The logit lens over prompts: for every layer ``l`` in ``[0, n_layers]`` the
+    share of prompts whose answer token (first token) is among the top ``topk``
+    tokens decoded from ``hook_resid_pre[l]`` at the last position (``l =
+    n_layers``: the model's own prediction), and the mean probability of the
+    answer there.  Returns ``(accuracy [n_layers + 1], probability [n_layers + 1])``."""
+    _check_prompts_answers(scrambled_prompts, prompt_answers)
+    if not 1 <= int(topk) <= _lib.STATS_MAX_K:
+        raise ValueError(f"topk must be in [1, {_lib.STATS_MAX_K}]")
+    prompts, answers = normalize_cie_inputs(model, scrambled_prompts, prompt_answers)
+    hits = prob = None
+    for a, b in _chunks(len(prompts), EXTRACT_BATCH):
+        seqs = prompts[a:b]
+        trace = model._sweep_trace(len(seqs), sum(len(s) for s in seqs))
+        model.forward_clean(seqs, trace=trace)
+        p, top = trace.logit_lens(answers[a:b], topk=int(topk))
+        tg = torch.as_tensor(answers[a:b], dtype=torch.int32, device=model.device)
+        h = (top == tg[:, None, None]).any(-1).sum(0)
+        p = p.sum(0)
+        hits, prob = (h, p) if hits is None else (hits + h, prob + p)
+    return hits.to(torch.float32) / len(prompts), prob / len(prompts)
+
+
+@range_checked
+def decode_vectors(vectors: torch.Tensor, k: int, model: Model = None) -> List[List[str]]:
+    """The ``k`` most likely next tokens each vector ``[n, d_model]`` (or one
+    ``[d_model]``) encodes, decoded through the final LayerNorm and the
+    unembedding, most likely first: the tables of decoded task vectors (Hendel
+    et al.) and function vectors (Todd et al.)."""
+    if not isinstance(vectors, torch.Tensor) or vectors.dim() not in (1, 2) or \
+            vectors.shape[-1] != model.cfg.d_model or vectors.numel() == 0:
+        raise ValueError("vectors must be of shape (n, d_model) or (d_model,)")
+    if not 1 <= int(k) <= _lib.STATS_MAX_K:
+        raise ValueError(f"k must be in [1, {_lib.STATS_MAX_K}]")
+    rows = vectors.to(model.device, torch.float32).reshape(-1, model.cfg.d_model)
+    _, top = model.decode_rows(rows, topk=int(k))
+    return [[model.to_string(t) for t in row] for row in top.tolist()]
 
 
 # ------------------------------------------------------------------- a6 / a7

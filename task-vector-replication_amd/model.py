@@ -9,7 +9,11 @@ token helpers, and drives the engine's batched entry points:
   launch sequence (replaces the per-site ``run_with_hooks`` loops);
 * ``project_heads``  — z-form capture → ``hook_result`` form;
 * ``capture_resid``  — grouped sums of ``hook_resid_pre`` rows of a trace, every
-  layer at once (replaces ``run_with_cache`` + a Python mean over prompts).
+  layer at once (replaces ``run_with_cache`` + a Python mean over prompts);
+* ``logit_attribution`` / ``head_attribution`` — every head's and every layer's
+  push on a token's logit from a trace (``stack_head_results`` + ``logit_attrs``);
+* ``logit_lens`` / ``decode_rows`` — residual rows of every layer, or any
+  vectors, through the final LayerNorm and the unembedding.
 
 The compute entry points run as torch.library operators (``torch.ops.tvr.*``,
 csrc/torch_ops.cpp over the C ABI) on torch's current stream, with outputs
@@ -162,6 +166,17 @@ class Trace:
         ``classes``: one id in ``[-1, n_classes)`` per traced token, flat or
         one list per sequence; ``-1`` is counted nowhere."""
         return self.model.capture_pattern(self, positions=pos, classes=classes, n_classes=n_classes)[1]
+
+    def logit_attribution(self, targets, contrast=None, pos: Optional[Sequence[int]] = None):
+        """Direct logit attribution at ``pos[s]`` of every traced sequence:
+        ``(heads [n_seq, L, H], resid [n_seq, L + 1])``; see ``Model.logit_attribution``."""
+        return self.model.logit_attribution(self, targets, contrast=contrast, positions=pos)
+
+    def logit_lens(self, targets=None, pos: Optional[Sequence[int]] = None, topk: int = 0):
+        """Every layer's residual row at ``pos[s]`` decoded through the final
+        LayerNorm and the unembedding: ``(prob [n_seq, L + 1] or None,
+        topk [n_seq, L + 1, k] or None)``; see ``Model.logit_lens``."""
+        return self.model.logit_lens(self, targets=targets, positions=pos, topk=topk)
 
     def _read(self, what: int, layer: int) -> torch.Tensor:
         m = self.model
@@ -638,6 +653,134 @@ class Model(TokenizerMixin):
         self._check_range("tvr_trace_capture_pattern")  # (a deferred clean forward may have run)
         trace._pending_out = None
         return pattern, mass
+
+    # ------------------------------------------- logit attribution and logit lens
+    def _trace_queries(self, trace: Trace, positions):
+        """The checks the trace readers below share: (n_seq, pos int32 [n] or None)."""
+        if trace.model is not self:
+            raise ValueError("trace belongs to another model")
+        lens = np.asarray(trace.seq_lens, dtype=np.int64)
+        n = int(lens.shape[0])
+        if n == 0:
+            raise ValueError("trace is empty: run forward_clean(trace=...) first")
+        pos = None
+        if positions is not None:
+            pos = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1)
+            if pos.shape[0] != n:
+                raise ValueError("positions must have one entry per traced sequence")
+            if np.any(pos < 0) or np.any(pos >= lens):
+                raise ValueError("a position lies outside its sequence")
+        return n, pos
+
+    def _token_ids(self, ids, n: int, name: str) -> np.ndarray:
+        a = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if a.shape[0] != n:
+            raise ValueError(f"{name} must have one entry per row")
+        if np.any(a < 0) or np.any(a >= self.cfg.d_vocab):
+            raise ValueError(f"a token of {name} lies outside [0, d_vocab)")
+        return a.astype(np.int32)
+
+    @staticmethod
+    def _check_topk(topk: int) -> int:
+        topk = int(topk)
+        if not 0 <= topk <= _lib.STATS_MAX_K:
+            raise ValueError(f"topk must be in [0, {_lib.STATS_MAX_K}]")
+        return topk
+
+    def head_attribution(self, layer: int, z: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
+        """How far each head of ``layer`` writes along a direction
+        (tvr_head_attribution): ``out[i, h] = (z[i, h·dh:(h+1)·dh] @ W_O[layer, h]) · dirs[i]``
+        for ``z``, ``dirs`` ``[n, d_model]`` (fp32 on the model device), ``[n, n_heads]``.
+        W_O is the processed fp32 weight ``project_heads`` reads.  The bits of a
+        row depend on that row alone."""
+        cfg = self.cfg
+        if not 0 <= int(layer) < cfg.n_layers:
+            raise ValueError("layer out of range")
+        for t, name in ((z, "z"), (dirs, "dirs")):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != cfg.d_model or t.shape[0] == 0:
+                raise ValueError(f"{name} must be a tensor [n, d_model]")
+            if t.device != self.device or t.dtype != torch.float32:
+                raise ValueError(f"{name} must be fp32 on the model device")
+        if z.shape[0] != dirs.shape[0]:
+            raise ValueError("z and dirs must have the same number of rows")
+        z, dirs = z.contiguous(), dirs.contiguous()
+        if z.data_ptr() % 16:
+            z = z.clone()
+        if dirs.data_ptr() % 16:
+            dirs = dirs.clone()
+        out = torch.empty(z.shape[0], cfg.n_heads, device=self.device)
+        self._op("head_attribution", self._h.value, int(layer), z, dirs, cfg.d_model, cfg.n_heads, out)
+        return out
+
+    def logit_attribution(self, trace: Trace, targets, contrast=None, positions: Optional[Sequence[int]] = None):
+        """Direct logit attribution at one query position per traced sequence
+        (tvr_trace_logit_attribution): ``(heads [n, L, H], resid [n, L + 1])``.
+        With ``u = W_U[:, target] − W_U[:, contrast]`` (processed weights; no
+        ``contrast``: the target's column) and the final LayerNorm's scale σ of
+        the query row, ``heads[s, l, h] = hook_result[l][q, h] · u / σ`` and
+        ``resid[s, l] = hook_resid_pre[l][q] · u / σ`` (``l = L``: the final
+        residual, i.e. logit[target] − logit[contrast] minus the same difference
+        of ``b_U``; ``l = 0``: the embedding's share).  TransformerLens:
+        ``cache.stack_head_results`` / ``accumulated_resid`` with
+        ``apply_ln=True`` under ``logit_attrs``.  ``positions`` defaults to every
+        sequence's last position.  Bitwise reproducible for a given trace."""
+        n, pos = self._trace_queries(trace, positions)
+        tg = self._token_ids(targets, n, "targets")
+        ct = self._token_ids(contrast, n, "contrast") if contrast is not None else None
+        cfg = self.cfg
+        heads = torch.empty(n, cfg.n_layers, cfg.n_heads, device=self.device)
+        resid = torch.empty(n, cfg.n_layers + 1, device=self.device)
+        self._op("logit_attribution", trace._h.value, torch.from_numpy(pos) if pos is not None else None,
+                 torch.from_numpy(tg), torch.from_numpy(ct) if ct is not None else None, n, cfg.n_layers,
+                 cfg.n_heads, heads, resid)
+        self._check_range("tvr_trace_logit_attribution")  # (a deferred clean forward may have run)
+        trace._pending_out = None
+        return heads, resid
+
+    def logit_lens(self, trace: Trace, targets=None, positions: Optional[Sequence[int]] = None, topk: int = 0):
+        """Every layer's residual row at the query position through the final
+        LayerNorm and the unembedding (tvr_trace_logit_lens): ``(prob, topk)``
+        with ``prob`` ``[n, L + 1]`` = softmax(logits)[target] (``targets``
+        given, else ``None``) and ``topk`` ``[n, L + 1, k]`` int32 token ids
+        (``topk > 0``, else ``None``).  Row ``L`` is the model's own
+        distribution at the query position."""
+        n, pos = self._trace_queries(trace, positions)
+        topk = self._check_topk(topk)
+        tg = self._token_ids(targets, n, "targets") if targets is not None else None
+        if tg is None and topk == 0:
+            raise ValueError("nothing to decode: give targets or topk > 0")
+        L = self.cfg.n_layers
+        prob = torch.empty(n, L + 1, device=self.device) if tg is not None else None
+        top = torch.empty(n, L + 1, topk, dtype=torch.int32, device=self.device) if topk else None
+        self._op("logit_lens", trace._h.value, torch.from_numpy(pos) if pos is not None else None,
+                 torch.from_numpy(tg) if tg is not None else None, n, L, topk, prob, top)
+        self._check_range("tvr_trace_logit_lens")
+        trace._pending_out = None
+        return prob, top
+
+    def decode_rows(self, rows: torch.Tensor, targets=None, topk: int = 0):
+        """Decode any vectors ``[n, d_model]`` (task vectors, function vectors,
+        residual rows) through the final LayerNorm and the unembedding
+        (tvr_decode_rows): ``(prob [n] or None, topk [n, k] int32 or None)``."""
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] != self.cfg.d_model or \
+                rows.shape[0] == 0:
+            raise ValueError("rows must be a tensor [n, d_model]")
+        if rows.device != self.device or rows.dtype != torch.float32:
+            raise ValueError("rows must be fp32 on the model device")
+        n = int(rows.shape[0])
+        topk = self._check_topk(topk)
+        tg = self._token_ids(targets, n, "targets") if targets is not None else None
+        if tg is None and topk == 0:
+            raise ValueError("nothing to decode: give targets or topk > 0")
+        rows = rows.contiguous()
+        if rows.data_ptr() % 16:
+            rows = rows.clone()
+        prob = torch.empty(n, device=self.device) if tg is not None else None
+        top = torch.empty(n, topk, dtype=torch.int32, device=self.device) if topk else None
+        self._op("decode_rows", self._h.value, rows, torch.from_numpy(tg) if tg is not None else None, topk,
+                 self.cfg.d_model, prob, top)
+        self._check_range("tvr_decode_rows")
+        return prob, top
 
     def project_heads(self, zsum: torch.Tensor) -> torch.Tensor:
         """[L, d] z-sums → [L, H, d] hook_result sums."""
