@@ -406,7 +406,8 @@ int tvr_patch_sweep(tvr_model* model, tvr_trace* trace,
  *            TVR_SITE_REPLACE_HEAD_ALLPOS read `vectors` with 16-byte loads:
  *            a launch that holds such a site with a base that is not 16-byte
  *            aligned returns TVR_ERR_INVALID here (tvr_patch_sweep does not
- *            check: pass it a 16-byte aligned base).  TVR_SITE_SET_RESID_PRE_VEC
+ *            check: pass it a 16-byte aligned base; the test primitive
+ *            tvr_site_entry does check, with or without sets).  TVR_SITE_SET_RESID_PRE_VEC
  *            reads it element-wise: float alignment suffices in both sweeps.
  * A set site enters the staircase at its lowest patched layer and computes
  * every layer from there (ALLPOS: all T rows; LASTPOS: the last row, against
@@ -639,6 +640,75 @@ typedef struct tvr_gemm_args {
   const int32_t* out_rows;
 } tvr_gemm_args;
 int tvr_gemm_launch(tvr_model* model, const tvr_gemm_args* args, void* stream);
+
+/* The site entry of the patch sweeps alone, on a caller's rows: the sites are
+ * planned exactly as tvr_patch_sweep / tvr_patch_sweep_sets plan them on a
+ * filled trace (entry layers, shared prefixes, head groups), every entry layer
+ * 0 .. n_layers runs the sweep's own entry launches, and the rows each site
+ * materialises (its resid_pre at its entry layer) are left in `out`.  Nothing
+ * else of a sweep runs.
+ *   seq_lens   host [n_seq], each in [1, n_ctx]: sequence s is the rows
+ *              [sum of the lengths before it, + seq_lens[s]) of every layer
+ *   token_ids  host [sum seq_lens] or NULL.  Given (and TVR_PREFIX_SHARE not 0):
+ *              REPLACE_HEAD sites share prefixes as in the sweep, so a follower
+ *              materialises the positions [p0, T) only
+ *   tokens     rows per layer of resid and z (>= sum seq_lens)
+ *   resid      device [n_layers + 1][tokens][d]: hook_resid_pre, the trace's layout
+ *   z          device [n_layers][tokens][d]: attn.hook_z
+ *   sites, vectors, n_vectors   as tvr_patch_sweep
+ *   set_off, patches            as tvr_patch_sweep_sets, or both NULL: the plain
+ *              sweep's planning (a head-set site enters as a copy of its clean rows)
+ *   flags      TVR_ENTRY_FORCE_VALU: REPLACE_HEAD sites take entry_kernel's own
+ *              VALU branch (the fallback for head sizes without an MFMA entry
+ *              kernel) instead of the MFMA kernel
+ *   out        device [out_rows][d]: site i's rows are
+ *              out[site_row0[i] .. site_row0[i] + site_rows[i]), the positions
+ *              [site_p0[i], site_p0[i] + site_rows[i]) of its sequence; rows past
+ *              the sum of site_rows are not written
+ *   site_row0, site_rows, site_p0   host [n_sites]: the planner's values
+ * All arguments are validated on the host before any device call:
+ * TVR_ERR_INVALID for a null model / seq_lens / resid / z / sites / out / report
+ * array, n_seq <= 0, n_sites <= 0, a length outside [1, n_ctx], a layout that
+ * exceeds `tokens`, resid, z or out not 16-byte aligned, unknown flags, set_off
+ * or patches as tvr_patch_sweep_sets refuses them, every site the sweeps
+ * refuse, more rows than out_rows — and, stricter than tvr_patch_sweep, a
+ * REPLACE_HEAD site with `vectors` not 16-byte aligned (its kernels load 16
+ * bytes).  A test primitive: it copies the tables to a temporary device buffer
+ * and synchronises `stream`.  (Backward-compatible addition: ABI 11.) */
+enum { TVR_ENTRY_FORCE_VALU = 1 };
+int tvr_site_entry(tvr_model* model, const int32_t* seq_lens, int32_t n_seq, const int32_t* token_ids,
+                   int32_t tokens, const float* resid, const float* z, const tvr_site* sites,
+                   int32_t n_sites, const int32_t* set_off, const tvr_head_patch* patches,
+                   const float* vectors, int32_t n_vectors, int32_t flags, float* out, int32_t out_rows,
+                   int32_t* site_row0, int32_t* site_rows, int32_t* site_p0, void* stream);
+
+/* One head-set patch launch (what a layer of tvr_patch_sweep_sets applies between
+ * the attention and the O + MLP-out GEMM) on a caller's buffers: for every item,
+ * the listed heads' d_head columns of a2 rows [row0, row0 + n_rows) become zero
+ * in every plane, and resid rows [row0, row0 + n_rows) += the sum of the listed
+ * vectors: s = ((0 + v0) + v1) + .. in list order, then x + s (fp32).
+ *   fmt      0: a2 is fp32 [rows][K2], K2 = d_model + d_mlp; TVR_GEMM_X2F16,
+ *            TVR_ACT_X2F16_IL, TVR_GEMM_BF16: halves [rows][2 K2] in the format
+ *            tvr_act_rows describes (BF16: the first K2 halves of a row)
+ *   items    host [n_items]: rows and the range [first_patch, first_patch +
+ *            n_patches) of `patches` (an empty range: nothing is zeroed, s = 0)
+ *   patches  host [n_patches]: (head, vec)
+ *   vectors  device [n_vectors][d], any float alignment (16-byte aligned with
+ *            d % 4 == 0 takes the float4 variant, else the element-wise one)
+ *   a2, resid  device, 16-byte aligned; resid [rows][d]
+ * All arguments are validated on the host before any device call:
+ * TVR_ERR_INVALID for a null model / items / vectors / a2 / resid, null patches
+ * with n_patches > 0, n_items <= 0, n_patches < 0, rows <= 0, an unknown fmt, a2
+ * or resid not 16-byte aligned, vectors not float aligned, an item with
+ * n_rows < 1, rows outside [0, rows) or shared with another item, a patch range
+ * outside the list, a head outside [0, n_heads), a vec outside [0, n_vectors).
+ * A test primitive: it copies the tables to a temporary device buffer and
+ * synchronises `stream`.  (Backward-compatible addition: ABI 11.) */
+typedef struct tvr_headset_item { int32_t row0, n_rows, first_patch, n_patches; } tvr_headset_item;
+typedef struct tvr_headset_patch { int32_t head, vec; } tvr_headset_patch;
+int tvr_headset_apply(tvr_model* model, int32_t fmt, const tvr_headset_item* items, int32_t n_items,
+                      const tvr_headset_patch* patches, int32_t n_patches, const float* vectors,
+                      int32_t n_vectors, void* a2, float* resid, int32_t rows, void* stream);
 
 /* Kernel timing (HIP events recorded on the launch stream around every GEMM
  * launch while enabled).  tvr_profile_read synchronises the recorded events

@@ -69,6 +69,19 @@ class CHeadPatch(ctypes.Structure):
     _fields_ = [("layer", ctypes.c_int32), ("head", ctypes.c_int32), ("vec", ctypes.c_int32)]
 
 
+class CHeadsetItem(ctypes.Structure):
+    """Mirror of ``tvr_headset_item`` (include/tvr.h; tvr_headset_apply, the head-set test primitive)."""
+    _fields_ = [("row0", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("first_patch", ctypes.c_int32),
+                ("n_patches", ctypes.c_int32)]
+
+
+class CHeadsetPatch(ctypes.Structure):
+    _fields_ = [("head", ctypes.c_int32), ("vec", ctypes.c_int32)]
+
+
+ENTRY_FORCE_VALU = 1  # include/tvr.h TVR_ENTRY_FORCE_VALU (tvr_site_entry, the site-entry test primitive)
+
+
 class CAttnSeq(ctypes.Structure):
     """Mirror of ``tvr_attn_seq`` (include/tvr.h; the kernels' SeqDesc)."""
     _fields_ = [("row0", ctypes.c_int32), ("n", ctypes.c_int32), ("p0", ctypes.c_int32),
@@ -197,6 +210,13 @@ SIGNATURES = {
                                        ctypes.c_int32, ctypes.c_void_p]),
     "tvr_trace_logit_lens": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_f32p, c_i32p, ctypes.c_int32,
                                             ctypes.c_void_p]),
+    "tvr_site_entry": (ctypes.c_int, [ctypes.c_void_p, c_i32p, ctypes.c_int32, c_i32p, ctypes.c_int32, c_f32p, c_f32p,
+                                      ctypes.c_void_p, ctypes.c_int32, c_i32p, ctypes.c_void_p, c_f32p,
+                                      ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32, c_i32p, c_i32p, c_i32p,
+                                      ctypes.c_void_p]),
+    "tvr_headset_apply": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_void_p,
+                                         c_f32p, ctypes.c_int32, ctypes.c_void_p]),
 }
 
 OPS_PATH = LIB_PATH.parent / OPS_NAME

@@ -2540,22 +2540,25 @@ struct SweepCtx {
   uint16_t* vg;  // exact-fp16 weights: one layer's G rows (centred vectors x LN1 / LN2 gamma, activation format)
 };
 
-// The sites entering at layer l (L: the final norm's input) materialise their residual rows.
-static int sweep_enter(const SweepCtx& cx, int l) {
+// The sites entering at layer l (L: the final norm's input) materialise their residual rows.  resid_base / z_base:
+// the clean hook_resid_pre [L + 1] and attn.hook_z [L] planes, tstride floats apart (the trace's; tvr_site_entry:
+// a caller's).  force_valu (tvr_site_entry only): REPLACE_HEAD sites take entry_kernel's own branch.
+static int sweep_enter(const SweepCtx& cx, int l, const float* resid_base, const float* z_base, size_t tstride,
+                       bool force_valu = false) {
   tvr_model* m = cx.m;
   const SweepPlan& p = cx.p;
   const tvr_config& c = m->cfg;
   const int d = c.d_model, k0 = l > 0 ? p.cnt_le[l - 1] : 0, k1 = p.cnt_le[l];
   if (k1 <= k0) return TVR_OK;
-  const size_t tstride = (size_t)cx.trace->max_tokens * d;
   // the clean rows' hook_resid_pre: the live rows [0, Rc) in a fused sweep (the trace's copy is written by
   // this layer's LayerNorm, after the entry), else the trace
-  const float* snap = cx.fused ? cx.a.resid : cx.trace->resid + (size_t)l * tstride;
-  const float* zsnap = l > 0 ? cx.trace->z + (size_t)(l - 1) * tstride : nullptr;
+  const float* snap = cx.fused ? cx.a.resid : resid_base + (size_t)l * tstride;
+  const float* zsnap = l > 0 ? z_base + (size_t)(l - 1) * tstride : nullptr;
   const float* w2 = l > 0 ? m->layers[l - 1].w2 : nullptr;
   const dim3 eg(k1 - k0, (d + ENTRY_THREADS - 1) / ENTRY_THREADS);
   ProfSpan ps(m, cx.st);
-  const bool mf = p.eg_cnt[l] > 0 && (c.d_head == 16 || c.d_head == 64 || c.d_head == 80 || c.d_head == 128);
+  const bool mf = !force_valu && p.eg_cnt[l] > 0 &&
+                  (c.d_head == 16 || c.d_head == 64 || c.d_head == 80 || c.d_head == 128);
   if (mf) {
     const dim3 gg(p.eg_cnt[l], (d + ENTRY_COLS - 1) / ENTRY_COLS);
 #define TVR_ENTRY_MF(DH)                                                                                     \
@@ -2823,7 +2826,7 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
       a.qkv_mirror = tqkv;
       a.mirror_rows = Rc;
     }
-    TVR_TRY(sweep_enter(cx, l));
+    TVR_TRY(sweep_enter(cx, l, trace->resid, trace->z, tstride));
     if (Rl == 0) continue;
     a.hs_n = p.hs_beg[l + 1] - p.hs_beg[l];  // this layer's head-set patches (0 without set sites)
     if (a.hs_n > 0) {
@@ -2854,7 +2857,7 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
                            hipMemcpyDeviceToDevice, st));
     trace->pending = false;
   }
-  TVR_TRY(sweep_enter(cx, L));
+  TVR_TRY(sweep_enter(cx, L, trace->resid, trace->z, tstride));
   TVR_TRY(run_final(m, a.resid, (const int32_t*)(base + o_last), (const int32_t*)(base + o_tg), n_sites,
                     (float*)(base + o_xf), (float*)(base + o_lg), out_prob, out_topk, topk, out_logits, fmt, st));
   if (fused && (trace->p_prob || trace->p_topk))
@@ -3277,6 +3280,161 @@ int tvr_attention_pattern(tvr_model* m, const float* qkv, int32_t rows, const in
     rc = launch_pattern(m, fn, qkv, 0, 1, (const PatternSeq*)dbuf, n_seq, max_q + 1,
                         cls_bytes ? (const int32_t*)(dbuf + seq_bytes) : nullptr, n_classes, out_pattern, ld, out_mass,
                         cos_t, sin_t, st);
+  e = hipStreamSynchronize(st);
+  if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  (void)hipFree(dbuf);
+  return rc;
+}
+
+int tvr_site_entry(tvr_model* m, const int32_t* seq_lens, int32_t n_seq, const int32_t* token_ids, int32_t tokens,
+                   const float* resid, const float* z, const tvr_site* sites, int32_t n_sites,
+                   const int32_t* set_off, const tvr_head_patch* patches, const float* vectors,
+                   int32_t n_vectors, int32_t flags, float* out, int32_t out_rows, int32_t* site_row0,
+                   int32_t* site_rows, int32_t* site_p0, void* stream) {
+  // every check on the host, before any device call
+  const char* fn = "tvr_site_entry";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!m) return bad("null model");
+  if (!seq_lens) return bad("null seq_lens");
+  if (!resid || !z) return bad("null resid / z");
+  if (!sites) return bad("null sites");
+  if (!out) return bad("null out");
+  if (!site_row0 || !site_rows || !site_p0) return bad("null site_row0 / site_rows / site_p0");
+  if (n_seq <= 0) return bad("n_seq must be positive");
+  if (n_sites <= 0) return bad("n_sites must be positive");
+  if (tokens <= 0 || out_rows <= 0) return bad("tokens and out_rows must be positive");
+  if (n_vectors < 0) return bad("n_vectors is negative");
+  if (flags & ~TVR_ENTRY_FORCE_VALU) return bad("unknown flags " + std::to_string(flags));
+  if (((uintptr_t)resid | (uintptr_t)z | (uintptr_t)out) & 15) return bad("resid, z and out must be 16-byte aligned");
+  if ((uintptr_t)vectors & 3) return bad("vectors must be float aligned");
+  if ((set_off == nullptr) != (patches == nullptr) && !(set_off && set_off[n_sites] <= set_off[0]))
+    return bad("set_off and patches must both be given or both be null");
+  const tvr_config& c = m->cfg;
+  const int d = c.d_model, L = c.n_layers;
+  std::vector<int> seq_off(n_seq), seq_len(n_seq);
+  int64_t total = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    if (seq_lens[s] < 1 || seq_lens[s] > c.n_ctx)
+      return bad("a length outside [1, n_ctx] (sequence " + std::to_string(s) + ")");
+    seq_off[s] = (int)total;
+    seq_len[s] = seq_lens[s];
+    total += seq_lens[s];
+    if (total > tokens) return bad("the layout exceeds tokens (sequence " + std::to_string(s) + ")");
+  }
+  if (set_off) {
+    if (set_off[0] < 0) return bad("set_off[0] is negative");
+    for (int i = 0; i < n_sites; ++i)
+      if (set_off[i + 1] < set_off[i]) return bad("set_off decreases at site " + std::to_string(i));
+  }
+  const bool aligned16 = ((uintptr_t)vectors & 15) == 0;
+  for (int i = 0; i < n_sites; ++i)
+    if (sites[i].kind == TVR_SITE_REPLACE_HEAD_ALLPOS && !aligned16)  // (the plain sweep's planning does not check)
+      return bad("site " + std::to_string(i) + ": REPLACE_HEAD_ALLPOS needs 16-byte aligned vectors");
+  const SweepPlanIn in{L, c.n_heads, d, c.d_head, seq_off.data(), seq_len.data(), token_ids, n_seq, (int)total,
+                       false, token_ids != nullptr && prefix_share_enabled(), false, ENTRY_GROUP, n_vectors,
+                       vectors != nullptr, aligned16, 4.0, sites, n_sites, set_off, patches};
+  SweepPlan p;
+  std::string err;
+  if (plan_sweep(in, p, err) != TVR_OK) return bad(err);
+  if (p.R > out_rows) return bad("the sites materialise " + std::to_string(p.R) + " rows: more than out_rows");
+  for (int i = 0; i < n_sites; ++i) {
+    site_row0[i] = p.row0[i];
+    site_rows[i] = p.nrow[i];
+    site_p0[i] = p.p0[i];
+  }
+
+  // the tables the entry kernels read, in one temporary buffer
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t b_ents = align_up(p.ents.size() * sizeof(EntryDesc)), b_gidx = align_up(p.egidx.size() * sizeof(int32_t));
+  const size_t b_groups = p.egroups.size() * sizeof(EntryGroup);
+  char* dbuf = nullptr;
+  if (hipMalloc(&dbuf, b_ents + b_gidx + b_groups + kAlign) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TVR_ERR_NOMEM, std::string(fn) + ": descriptor buffer");
+  }
+  hipError_t e = hipMemcpyAsync(dbuf, p.ents.data(), p.ents.size() * sizeof(EntryDesc), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && !p.egidx.empty())
+    e = hipMemcpyAsync(dbuf + b_ents, p.egidx.data(), p.egidx.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && b_groups)
+    e = hipMemcpyAsync(dbuf + b_ents + b_gidx, p.egroups.data(), b_groups, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // pageable host memory
+  int rc = e == hipSuccess ? TVR_OK : fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  // the sites' rows are the activation rows [0, R) (no fused clean rows): the entry kernels write them to `out`
+  Acts a{out, nullptr, nullptr, nullptr, ACT_F32};
+  const SweepCtx cx{m, nullptr, p, false, a, vectors, st, nullptr, (const EntryDesc*)dbuf,
+                    (const int32_t*)(dbuf + b_ents), (const EntryGroup*)(dbuf + b_ents + b_gidx),
+                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int l = 0; l <= L && rc == TVR_OK; ++l)
+    rc = sweep_enter(cx, l, resid, z, (size_t)tokens * d, (flags & TVR_ENTRY_FORCE_VALU) != 0);
+  e = hipStreamSynchronize(st);
+  if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  (void)hipFree(dbuf);
+  return rc;
+}
+
+static_assert(sizeof(tvr_headset_item) == sizeof(HeadsetItem) && sizeof(tvr_headset_patch) == sizeof(HeadsetPatch),
+              "tvr_headset_item / tvr_headset_patch are HeadsetItem / HeadsetPatch");
+
+int tvr_headset_apply(tvr_model* m, int32_t fmt, const tvr_headset_item* items, int32_t n_items,
+                      const tvr_headset_patch* patches, int32_t n_patches, const float* vectors, int32_t n_vectors,
+                      void* a2, float* resid, int32_t rows, void* stream) {
+  // every check on the host, before any device call
+  const char* fn = "tvr_headset_apply";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!m) return bad("null model");
+  if (!items) return bad("null items");
+  if (!vectors) return bad("null vectors");
+  if (!a2 || !resid) return bad("null a2 / resid");
+  if (n_items <= 0) return bad("n_items must be positive");
+  if (n_patches < 0 || (n_patches > 0 && !patches)) return bad("n_patches is negative, or patches is null");
+  if (rows <= 0) return bad("rows must be positive");
+  if (n_vectors < 0) return bad("n_vectors is negative");
+  if (fmt != 0 && fmt != TVR_GEMM_X2F16 && fmt != TVR_ACT_X2F16_IL && fmt != TVR_GEMM_BF16)
+    return bad("unknown fmt " + std::to_string(fmt));
+  if (fmt == TVR_ACT_X2F16_IL && m->K2 % 32 != 0) return bad("the interleaved format needs K2 % 32 == 0");
+  if (((uintptr_t)a2 | (uintptr_t)resid) & 15) return bad("a2 and resid must be 16-byte aligned");
+  if ((uintptr_t)vectors & 3) return bad("vectors must be float aligned");
+  const tvr_config& c = m->cfg;
+  std::vector<std::pair<int64_t, int64_t>> spans;
+  int max_rows = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const tvr_headset_item& it = items[i];
+    const std::string at = " (item " + std::to_string(i) + ")";
+    if (it.n_rows < 1) return bad("n_rows must be at least 1" + at);
+    if (it.row0 < 0 || (int64_t)it.row0 + it.n_rows > rows) return bad("rows [row0, row0 + n_rows) outside the buffers" + at);
+    if (it.first_patch < 0 || it.n_patches < 0 || (int64_t)it.first_patch + it.n_patches > n_patches)
+      return bad("patch range outside the list" + at);
+    for (int q = it.first_patch; q < it.first_patch + it.n_patches; ++q) {
+      if (patches[q].head < 0 || patches[q].head >= c.n_heads) return bad("head out of range" + at);
+      if (patches[q].vec < 0 || patches[q].vec >= n_vectors) return bad("vector out of range" + at);
+    }
+    spans.emplace_back(it.row0, (int64_t)it.row0 + it.n_rows);
+    max_rows = std::max(max_rows, it.n_rows);
+  }
+  std::sort(spans.begin(), spans.end());
+  for (size_t i = 1; i < spans.size(); ++i)
+    if (spans[i].first < spans[i - 1].second) return bad("two items share rows");  // (their residual sums would race)
+
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t b_items = align_up((size_t)n_items * sizeof(HeadsetItem));
+  char* dbuf = nullptr;
+  if (hipMalloc(&dbuf, b_items + (size_t)n_patches * sizeof(HeadsetPatch) + kAlign) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TVR_ERR_NOMEM, std::string(fn) + ": descriptor buffer");
+  }
+  hipError_t e = hipMemcpyAsync(dbuf, items, (size_t)n_items * sizeof(HeadsetItem), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && n_patches > 0)
+    e = hipMemcpyAsync(dbuf + b_items, patches, (size_t)n_patches * sizeof(HeadsetPatch), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // pageable host memory
+  int rc = e == hipSuccess ? TVR_OK : fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  Acts a{resid, nullptr, nullptr, (float*)a2,
+         fmt == 0 ? ACT_F32 : fmt == TVR_GEMM_X2F16 ? ACT_X2F16 : fmt == TVR_ACT_X2F16_IL ? ACT_X2F16I : ACT_BF16};
+  a.hs_items = (const HeadsetItem*)dbuf;
+  a.hs_patches = (const HeadsetPatch*)(dbuf + b_items);
+  a.hs_vectors = vectors;
+  a.hs_n = n_items;
+  a.hs_max_rows = max_rows;
+  if (rc == TVR_OK) rc = apply_headset(m, a, st);
   e = hipStreamSynchronize(st);
   if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
   (void)hipFree(dbuf);
