@@ -554,9 +554,12 @@ int tvr_head_attribution(tvr_model* model, int32_t layer, const float* z, const 
  * (Backward-compatible addition: ABI 11.) */
 int tvr_decode_rows(tvr_model* model, const float* rows, int32_t n, const int32_t* targets, float* out_prob,
                     int32_t* out_topk, int32_t topk, void* stream);
-/* One planar GEMM through the engine's own dispatch (launch_gemm: the skinny
- * kernel, gemm_pingpong_kernel plain, split over K, with a split tail or
- * stream-K and their reduce kernels), C = A W^T under one fused epilogue.  The
+/* One planar GEMM through the engine's own dispatch (engine.hip launch_gemm:
+ * the skinny kernel, or gemm_pingpong_kernel plain, split over K, with a split
+ * tail or stream-K and their reduce kernels, each picked by the selectors of
+ * gemm_pingpong.hpp, pp_kernel / pp_reduce_kernel; a form they do not hold is
+ * TVR_ERR_INTERNAL, which no checked argument reaches), C = A W^T under one
+ * fused epilogue.  The
  * split-K workspace lives on the model; a tiny model is enough, its weights are
  * not used.
  *   fmt      TVR_GEMM_X2F16, TVR_ACT_X2F16_IL or TVR_GEMM_BF16: A (and a2) in
@@ -593,7 +596,8 @@ int tvr_decode_rows(tvr_model* model, const float* rows, int32_t n, const int32_
  *            ways; TVR_FORM_STREAMK tiles [0, form_tile) plain, the rest
  *            stream-K over form_n blocks
  *   slicing  the x2f16 sliced accumulation: TVR_SLICE_MODEL the engine's rule
- *            (K or the model's K2 >= 16384), TVR_SLICE_ON, TVR_SLICE_OFF
+ *            (pp_sliced_rule: K or the model's K2 >= 16384), TVR_SLICE_ON,
+ *            TVR_SLICE_OFF
  * All arguments are validated on the host before any device call and before
  * the model is read: TVR_ERR_INVALID for a null model / args / A / W / out0, an
  * unknown fmt, exact16, epi, form, slicing or skinny, M, N or K <= 0, K not a
@@ -761,7 +765,8 @@ int tvr_profile_read_hbm(tvr_model* model, tvr_hbm_stats* out);
  * the QKV + MLP-in launch (GELU epilogue); bit 1 (TVR_PLAN_MODEL_SLICED): the
  * launch belongs to a model whose O + MLP-out K reaches the sliced-accumulation
  * threshold (6.9B, 12B: every x2f16 GEMM of such a model runs sliced, as does
- * any launch with K >= that threshold); bit 2 (TVR_PLAN_EXACT16): one exact
+ * any launch with K >= that threshold; pp_sliced_rule, the one statement of it
+ * that launch_gemm and this entry point share); bit 2 (TVR_PLAN_EXACT16): one exact
  * fp16 weight plane (tvr_model_set_exact16: 2 products, cheaper k-tiles).
  * Host-only, no device call (diagnostics, CPU tests).  (ABI 10; flag bits 1
  * and 2 from round 5) */

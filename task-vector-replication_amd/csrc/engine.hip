@@ -358,8 +358,6 @@ bool act_layout_interleaved() {
 // which only the one-plane GEMM reads; the side buffers (vact, vg, G) keep act_fmt's planar layout.
 int acts_fmt(const tvr_model* m) { return use_x16(m) && m->act_il ? (int)ACT_X2F16I : act_fmt(m); }
 
-// gemm_pingpong_kernel over tiles [tile_base, tile_base + count) of a planar
-// launch's raster (count 0: all), VEC epilogue
 // Raster group (m-blocks walked before the next block column): 4, or 2 when
 // there are at most 16 block columns (tools/gemm_split_probe x2ppgm<N>: at
 // M = 90,000 the qkv shape ran 459 / 451 / 419 TF at 4 / 8 / 16, the
@@ -374,87 +372,38 @@ int pp_group_m(int N) {
   return (N + 255) / 256 <= 16 ? small : large;
 }
 
-// ail: A in the interleaved x2f16 layout (a_fmt ACT_X2F16; launch_gemm checks the combinations)
-void launch_pp(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, int ldw, int M, int N, int K,
-               const GemmEpi& ep0, float acc_scale, int tile_base, int count, bool vec, bool sl, hipStream_t st,
-               bool ail = false) {
+// gemm_pingpong_kernel `kp` (pp_kernel of the launch's form) over tiles [tile_base, tile_base + count) of a
+// planar launch's raster (count 0: all)
+void launch_pp(PpKernel kp, const uint16_t* Ah, int lda, const MatW& W, int ldw, int M, int N, int K,
+               const GemmEpi& ep0, float acc_scale, int tile_base, int count, hipStream_t st) {
   GemmEpi ep = ep0;
   ep.tile_base = tile_base;
   ep.tile_count = count;
   ep.group_m = pp_group_m(N);
   const dim3 g(count > 0 ? count : gemm_pingpong_grid(M, N));
-  const bool wx = a_fmt == ACT_X2F16 && W.x16;  // one exact fp16 weight plane: 2 products (launch_gemm checks)
-#define TVR_PP1(E, F, V, S, X)                                                                                    \
-  hipLaunchKernelGGL((gemm_pingpong_kernel<E, F, V, 0, false, S, X>), g, dim3(PP_THREADS), 0, st, Ah, 2 * lda,    \
-                     (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, ep)
-#define TVR_PP1V(E, F, S, X) \
-  if (vec) { TVR_PP1(E, F, true, S, X); } else { TVR_PP1(E, F, false, S, X); }
-#define TVR_PP1F(E)                                                                                \
-  if (a_fmt == ACT_X2F16) {                                                                        \
-    if (wx) {                                                                                      \
-      if (sl) { TVR_PP1V(E, ACT_X2F16, true, true); } else { TVR_PP1V(E, ACT_X2F16, false, true); } \
-    } else {                                                                                       \
-      if (sl) { TVR_PP1V(E, ACT_X2F16, true, false); } else { TVR_PP1V(E, ACT_X2F16, false, false); } \
-    }                                                                                              \
-  } else {                                                                                         \
-    TVR_PP1V(E, ACT_BF16, false, false);                                                           \
-  }
-  if (a_fmt == ACT_F16) {  // the bf16 mode's Q / K columns: plain fp32 outputs only (launch_gemm checks)
-    TVR_PP1V(EPI_BIAS, ACT_F16, false, false);
-    return;
-  }
-  if (ail) {  // one-plane weights: every epilogue; two weight planes (the primitive ABI entry point): EPI_BIAS
-#define TVR_PPI(E, V, S, X)                                                                                          \
-  hipLaunchKernelGGL((gemm_pingpong_kernel<E, ACT_X2F16, V, 0, false, S, X, true>), g, dim3(PP_THREADS), 0, st, Ah, \
-                     2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, ep)
-#define TVR_PPIV(E, X)                                                             \
-  if (vec) {                                                                       \
-    if (sl) { TVR_PPI(E, true, true, X); } else { TVR_PPI(E, true, false, X); }    \
-  } else {                                                                         \
-    if (sl) { TVR_PPI(E, false, true, X); } else { TVR_PPI(E, false, false, X); }  \
-  }
-    if (!wx) {
-      TVR_PPIV(EPI_BIAS, false);
-    } else {
-      switch (epi) {
-        case EPI_BIAS: TVR_PPIV(EPI_BIAS, true); break;
-        case EPI_SPLIT_GELU_ACT: TVR_PPIV(EPI_SPLIT_GELU_ACT, true); break;
-        case EPI_STATS:
-          if (sl) { TVR_PPI(EPI_STATS, true, true, true); } else { TVR_PPI(EPI_STATS, true, false, true); }
-          break;
-        default: TVR_PPIV(EPI_RESID, true); break;
-      }
-    }
-#undef TVR_PPIV
-#undef TVR_PPI
-    return;
-  }
-  switch (epi) {
-    case EPI_BIAS: TVR_PP1F(EPI_BIAS); break;
-    case EPI_SPLIT_GELU_ACT: TVR_PP1F(EPI_SPLIT_GELU_ACT); break;
-    case EPI_STATS:  // LDS epilogue only (vec: N % 4 == 0, host-checked)
-      if (a_fmt != ACT_X2F16) {
-        TVR_PP1(EPI_STATS, ACT_BF16, true, false, false);
-      } else if (sl) {
-        if (wx) { TVR_PP1(EPI_STATS, ACT_X2F16, true, true, true); } else { TVR_PP1(EPI_STATS, ACT_X2F16, true, true, false); }
-      } else {
-        if (wx) { TVR_PP1(EPI_STATS, ACT_X2F16, true, false, true); } else { TVR_PP1(EPI_STATS, ACT_X2F16, true, false, false); }
-      }
-      break;
-    default: TVR_PP1F(EPI_RESID); break;
-  }
-#undef TVR_PP1F
-#undef TVR_PP1V
-#undef TVR_PP1
+  hipLaunchKernelGGL(kp, g, dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, ep);
 }
 
-// The same tiles with K split over `ksplit` blocks per tile: fp32 partial
-// tiles to the model's split-K workspace, then splitk_reduce_kernel sums them
-// in order and applies the epilogue (deterministic).
-int launch_pp_splitk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, int ldw, int M, int N, int K,
-                     const GemmEpi& ep0, float acc_scale, int tile_base, int count, int ksplit, bool sl, tvr_model* m,
-                     hipStream_t st, bool ail = false) {
-  const int rc = ensure_splitk(m, (size_t)ksplit * count * PP_TILE_ELEMS * sizeof(float), st);
+// One planned planar GEMM, resolved before anything is launched (resolve_pp): tiles [0, base) by `whole`, and
+// with n > 0 the tiles from `base` on as fp32 partial tiles, split-K n ways or stream-K over n blocks.
+struct PpLaunch {
+  PpKernel whole = nullptr;              // the launch's own epilogue (n == 0: every tile)
+  PpKernel partial = nullptr;            // EPI_BIAS, VEC partial tiles
+  PpReduceKernel reduce = nullptr;       // after split-K partials
+  PpSkReduceKernel sk_reduce = nullptr;  // after stream-K partials
+  bool skm = false;
+  int base = 0, n = 0;
+};
+
+// The partial range of `pl`: tiles [base, base + count) as fp32 partial tiles in the model's split-K workspace,
+// then the reduce kernel, which sums each tile's partials in k order and applies the epilogue (deterministic).
+// Split-K: K split over n blocks per tile (splitk_reduce_kernel).  Stream-K: n blocks share the range's
+// k-iterations evenly (gemm_pingpong_kernel sk_blocks; splitk_sk_reduce_kernel).
+int launch_pp_partial(const PpLaunch& pl, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, int ldw, int M, int N,
+                      int K, const GemmEpi& ep0, float acc_scale, int count, tvr_model* m, hipStream_t st) {
+  const int n = pl.n;
+  const size_t ws_tiles = pl.skm ? (size_t)2 * n : (size_t)n * count;
+  const int rc = ensure_splitk(m, ws_tiles * PP_TILE_ELEMS * sizeof(float), st);
   if (rc != TVR_OK) return rc;
   GemmEpi ep = ep0;  // the reduce's epilogue: same raster as the partial launch
   ep.group_m = pp_group_m(N);
@@ -462,115 +411,20 @@ int launch_pp_splitk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW
   pe.group_m = ep.group_m;
   pe.out0 = m->splitk_ws;
   pe.a_rows = ep.a_rows;
-  pe.k_split = ksplit;
-  pe.tile_base = tile_base;
+  if (pl.skm) pe.sk_blocks = n; else pe.k_split = n;
+  pe.tile_base = pl.base;
   pe.tile_count = count;
-  const dim3 g(count * ksplit), rg((unsigned)std::min<long>(4096, ((long)count * (PP_TILE_ELEMS / 4) + 255) / 256));
   pe.a2 = ep.a2;  // the exact-fp16 QKV + MLP-in launch's second A operand (by column)
   pe.a2_col = ep.a2_col;
-  const bool wx = a_fmt == ACT_X2F16 && W.x16;
-  if (ail && sl)  // (one-plane weights: launch_gemm checks)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, true, true, true>), g,
-                       dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (ail)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, false, true, true>), g,
-                       dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_X2F16 && wx && sl)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, true, true>), g, dim3(PP_THREADS), 0,
-                       st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_X2F16 && wx)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, false, true>), g, dim3(PP_THREADS), 0,
-                       st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_X2F16 && sl)  // sliced accumulation (gemm_pingpong.hpp)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, false, true>), g, dim3(PP_THREADS), 0, st,
-                       Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_X2F16)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true>), g, dim3(PP_THREADS), 0, st, Ah, 2 * lda,
-                       (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_F16)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_F16, true>), g, dim3(PP_THREADS), 0, st, Ah, 2 * lda,
-                       (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
+  const dim3 g(pl.skm ? n : count * n);
+  const dim3 rg((unsigned)std::min<long>(4096, ((long)count * (PP_TILE_ELEMS / 4) + 255) / 256));
+  hipLaunchKernelGGL(pl.partial, g, dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M,
+                     N, K, pe);
+  const float* part = (const float*)m->splitk_ws;
+  if (pl.skm)
+    hipLaunchKernelGGL(pl.sk_reduce, rg, dim3(256), 0, st, part, n, K / pp_ktile(a_fmt), pl.base, count, M, N, ep);
   else
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_BF16, true>), g, dim3(PP_THREADS), 0, st, Ah, 2 * lda,
-                       (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-#define TVR_SK_REDUCE(E, F)                                                                                     \
-  hipLaunchKernelGGL((splitk_reduce_kernel<E, F>), rg, dim3(256), 0, st, (const float*)m->splitk_ws, ksplit, \
-                     tile_base, count, M, N, ep)
-#define TVR_SK_REDUCE_F(E)                                          \
-  if (ail) { TVR_SK_REDUCE(E, ACT_X2F16I); }                        \
-  else if (a_fmt == ACT_X2F16) { TVR_SK_REDUCE(E, ACT_X2F16); }     \
-  else { TVR_SK_REDUCE(E, ACT_BF16); }
-  switch (epi) {
-    case EPI_BIAS: TVR_SK_REDUCE_F(EPI_BIAS); break;
-    case EPI_SPLIT_GELU_ACT: TVR_SK_REDUCE_F(EPI_SPLIT_GELU_ACT); break;
-    default: TVR_SK_REDUCE_F(EPI_RESID); break;
-  }
-#undef TVR_SK_REDUCE_F
-#undef TVR_SK_REDUCE
-  return TVR_OK;
-}
-
-// Stream-K over tiles [tile_base, tile_base + count): G blocks share their
-// k-iterations evenly (gemm_pingpong_kernel sk_blocks), fp32 partial tiles to
-// the model's split-K workspace, then splitk_sk_reduce_kernel sums each tile's
-// partials in k order and applies the epilogue (deterministic).
-int launch_pp_sk(int epi, const uint16_t* Ah, int lda, int a_fmt, const MatW& W, int ldw, int M, int N, int K,
-                 const GemmEpi& ep0, float acc_scale, int tile_base, int count, int G, bool sl, tvr_model* m,
-                 hipStream_t st, bool ail = false) {
-  const int rc = ensure_splitk(m, (size_t)2 * G * PP_TILE_ELEMS * sizeof(float), st);
-  if (rc != TVR_OK) return rc;
-  GemmEpi ep = ep0;
-  ep.group_m = pp_group_m(N);
-  GemmEpi pe{};
-  pe.group_m = ep.group_m;
-  pe.out0 = m->splitk_ws;
-  pe.a_rows = ep.a_rows;
-  pe.sk_blocks = G;
-  pe.tile_base = tile_base;
-  pe.tile_count = count;
-  const dim3 g(G), rg((unsigned)std::min<long>(4096, ((long)count * (PP_TILE_ELEMS / 4) + 255) / 256));
-  pe.a2 = ep.a2;
-  pe.a2_col = ep.a2_col;
-  const bool wx = a_fmt == ACT_X2F16 && W.x16;
-  if (ail && sl)  // (one-plane weights: launch_gemm checks)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true, true, true, true>), g,
-                       dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (ail)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true, false, true, true>), g,
-                       dim3(PP_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_X2F16 && wx && sl)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true, true, true>), g, dim3(PP_THREADS), 0, st,
-                       Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_X2F16 && wx)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true, false, true>), g, dim3(PP_THREADS), 0,
-                       st, Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_X2F16 && sl)  // sliced accumulation (gemm_pingpong.hpp)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true, true>), g, dim3(PP_THREADS), 0, st,
-                       Ah, 2 * lda, (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_X2F16)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_X2F16, true, 0, true>), g, dim3(PP_THREADS), 0, st, Ah, 2 * lda,
-                       (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else if (a_fmt == ACT_F16)
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_F16, true, 0, true>), g, dim3(PP_THREADS), 0, st, Ah, 2 * lda,
-                       (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  else
-    hipLaunchKernelGGL((gemm_pingpong_kernel<EPI_BIAS, ACT_BF16, true, 0, true>), g, dim3(PP_THREADS), 0, st, Ah, 2 * lda,
-                       (size_t)lda, W.h, ldw, W.wps, acc_scale, M, N, K, pe);
-  const int KT = K / (a_fmt == ACT_X2F16 ? 32 : 64);
-#define TVR_SKR(E, F)                                                                                         \
-  hipLaunchKernelGGL((splitk_sk_reduce_kernel<E, F>), rg, dim3(256), 0, st, (const float*)m->splitk_ws, G, KT, \
-                     tile_base, count, M, N, ep)
-#define TVR_SKR_F(E)                                     \
-  if (ail) { TVR_SKR(E, ACT_X2F16I); }                   \
-  else if (a_fmt == ACT_X2F16) { TVR_SKR(E, ACT_X2F16); } \
-  else { TVR_SKR(E, ACT_BF16); }
-  switch (epi) {
-    case EPI_BIAS: TVR_SKR_F(EPI_BIAS); break;
-    case EPI_SPLIT_GELU_ACT: TVR_SKR_F(EPI_SPLIT_GELU_ACT); break;
-    default: TVR_SKR_F(EPI_RESID); break;
-  }
-#undef TVR_SKR_F
-#undef TVR_SKR
+    hipLaunchKernelGGL(pl.reduce, rg, dim3(256), 0, st, part, n, pl.base, count, M, N, ep);
   return TVR_OK;
 }
 
@@ -650,7 +504,7 @@ double plan_reduce_us(int M, int N, int t0, int cnt, int S) {
 // exact weight plane, 2 products (0.72 of the 3-product k-tile, 0.85 sliced: profiles/r05/wx_probe_r05r.jsonl)
 PpPlan plan_pp(int M, int N, int K, int a_fmt, int epi, bool sliced = false, bool wx = false) {
   PpPlan p;
-  const int tiles = gemm_pingpong_grid(M, N), nkt = K / (a_fmt == ACT_X2F16 ? 32 : 64);
+  const int tiles = gemm_pingpong_grid(M, N), nkt = K / pp_ktile(a_fmt);
   const double kt_scale = wx ? (sliced ? 0.85 : 0.72) : 1.0;
   const double kt_us = (a_fmt == ACT_X2F16 ? 1.9 : 1.3) * (sliced ? 1.13 : 1.0) * kt_scale, seg_us = 15.0,
                epi_us = 10.0;
@@ -724,11 +578,48 @@ PpPlan plan_pp_cached(tvr_model* m, int M, int N, int K, int a_fmt, int epi, boo
   const PlanKey key{M, N, K, a_fmt + (wx ? 16 : 0), epi == EPI_SPLIT_GELU_ACT ? 1 : epi == EPI_RESID ? 2 : 0, sk_mode()};
   auto it = m->plans.find(key);
   if (it != m->plans.end()) return it->second;
-  const PpPlan p = plan_pp(M, N, K, a_fmt, epi, a_fmt == ACT_X2F16 && (K >= PP_SLICE_MIN_K || m->K2 >= PP_SLICE_MIN_K),
-                           wx);
+  const PpPlan p = plan_pp(M, N, K, a_fmt, epi, a_fmt == ACT_X2F16 && pp_sliced_rule(K, m->K2), wx);
   if (m->plans.size() > 4096) m->plans.clear();
   m->plans.emplace(key, p);
   return p;
+}
+
+// The kernels and ranges of `plan` for a planar GEMM whose whole-epilogue form is `f`.  A form without an
+// instantiation is an engine error, not another form's launch (launch_gemm's argument checks keep every caller's
+// arguments off such a form).
+int resolve_pp(const PpForm& f, const PpPlan& plan, PpLaunch& pl) {
+  auto missing = [](const char* what, const PpForm& g) {
+    return fail(TVR_ERR_INTERNAL, std::string("gemm: no ") + what + " is instantiated for the form epi " +
+                                      std::to_string(g.epi) + ", fmt " + std::to_string(g.fmt) + ", vec " +
+                                      std::to_string(g.vec) + ", stream-K " + std::to_string(g.skm) + ", sliced " +
+                                      std::to_string(g.sl) + ", one weight plane " + std::to_string(g.wx) +
+                                      ", interleaved A " + std::to_string(g.ail));
+  };
+  pl.skm = plan.sk_base >= 0;
+  const bool whole_split = !pl.skm && plan.ksplit > 1, tail_split = !pl.skm && !whole_split && plan.tail_base > 0;
+  pl.base = pl.skm ? plan.sk_base : tail_split ? plan.tail_base : 0;
+  pl.n = pl.skm ? plan.sk_blocks : whole_split ? plan.ksplit : tail_split ? plan.tail_split : 0;
+  if (pl.n == 0 || pl.base > 0) {
+    PpForm whole = f;
+    whole.vec = f.vec || pl.n > 0;  // the tiles ahead of a partial range run the vector epilogue (a plan needs it)
+    pl.whole = pp_kernel(whole);
+    if (!pl.whole) return missing("gemm_pingpong_kernel", whole);
+  }
+  if (pl.n > 0) {
+    PpForm part = f;  // fp32 partial tiles
+    part.epi = EPI_BIAS;
+    part.vec = true;
+    part.skm = pl.skm;
+    pl.partial = pp_kernel(part);
+    if (!pl.partial) return missing("partial-tile gemm_pingpong_kernel", part);
+    const int out_fmt = pp_reduce_fmt(f.fmt, f.ail);
+    if (pl.skm)
+      pl.sk_reduce = pp_reduce_kernel<true>(f.epi, out_fmt);
+    else
+      pl.reduce = pp_reduce_kernel<false>(f.epi, out_fmt);
+    if (!pl.sk_reduce && !pl.reduce) return missing("reduce kernel", part);
+  }
+  return TVR_OK;
 }
 
 // C = A @ W^T with epilogue `epi`.  A is fp32 [M][lda] (a_fmt ACT_F32:
@@ -769,6 +660,33 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
       ((a_fmt == ACT_BF16 || a_fmt == ACT_F16) && K % 64 != 0))
     return fail(TVR_ERR_UNSUPPORTED, "gemm: K, lda, ldw must be multiples of 32/4/4 (8 for planes, K of 64 for "
                                      "bf16; K=" + std::to_string(K) + ")");
+  // the planar launch's form, plan and kernels, before any event or launch
+  const bool wx = a_fmt == ACT_X2F16 && W.x16;  // one exact fp16 weight plane: 2 products per k-step
+  bool vec = false, sl = false, skinny = false;
+  PpLaunch pl;
+  if (planar) {
+    vec = planar_epilogue_vec(epi, ep, N);
+    // x2f16 sliced accumulation (gemm_pingpong.hpp) on every GEMM of a model whose O + MLP-out K reaches
+    // PP_SLICE_MIN_K (6.9B, 12B), or on any launch of that K
+    // (one-plane weights, A/B of the precision it costs: TVR_WX_SLICE=0 runs them unsliced, 2 slices the
+    // O + MLP-out launches only)
+    static const int wx_slice = env_int("TVR_WX_SLICE", 1);
+    sl = force && force->slicing ? a_fmt == ACT_X2F16 && force->slicing == 1
+                                 : a_fmt == ACT_X2F16 && pp_sliced_rule(K, m ? m->K2 : 0) &&
+                                       (!wx || wx_slice == 1 || (wx_slice == 2 && epi == EPI_RESID));
+    // a few rows (the linearised entry's G on a rank of a head split): gemm_skinny.hpp
+    skinny = ep.skinny && epi == EPI_BIAS && M <= SK_USE_M && !ep.out_rows && ep.k_split <= 1 && vec &&
+             a_fmt != ACT_F16 && !wx && !ep.a2 && !ail;
+    if (!skinny) {
+      PpPlan plan;
+      if (force && force->plan_set)
+        plan = force->plan;
+      else if (m && vec && epi != EPI_STATS)
+        plan = plan_pp_cached(m, M, N, K, a_fmt, epi, wx);
+      // EPI_STATS has the LDS (vector) epilogue only, whatever planar_epilogue_vec said (N % 4 == 0: above)
+      TVR_TRY(resolve_pp(PpForm{epi, a_fmt, vec || epi == EPI_STATS, false, sl, wx, ail}, plan, pl));
+    }
+  }
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (m && m->prof) {
     ev0 = prof_event(m);
@@ -779,19 +697,7 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
   const float acc_scale = a_fmt == ACT_BF16 ? 1.0f : a_fmt == ACT_F16 ? 1.0f / W.wscale : 1.0f / (W.wscale * X2_ASCALE);
   if (planar) {
     const uint16_t* Ah = static_cast<const uint16_t*>(A);
-    const bool vec = planar_epilogue_vec(epi, ep, N);
-    // x2f16 sliced accumulation (gemm_pingpong.hpp) on every GEMM of a model whose O + MLP-out K reaches
-    // PP_SLICE_MIN_K (6.9B, 12B), or on any launch of that K
-    // (one-plane weights, A/B of the precision it costs: TVR_WX_SLICE=0 runs them unsliced, 2 slices the
-    // O + MLP-out launches only)
-    static const int wx_slice = env_int("TVR_WX_SLICE", 1);
-    const bool sl = force && force->slicing
-                        ? a_fmt == ACT_X2F16 && force->slicing == 1
-                        : a_fmt == ACT_X2F16 && (K >= PP_SLICE_MIN_K || (m && m->K2 >= PP_SLICE_MIN_K)) &&
-                              (!W.x16 || wx_slice == 1 || (wx_slice == 2 && epi == EPI_RESID));
-    if (ep.skinny && epi == EPI_BIAS && M <= SK_USE_M && !ep.out_rows && ep.k_split <= 1 && vec &&
-        a_fmt != ACT_F16 && !W.x16 && !ep.a2 && !ail) {
-      // a few rows (the linearised entry's G on a rank of a head split): gemm_skinny.hpp
+    if (skinny) {
       const dim3 g(gemm_skinny_grid(N));
 #define TVR_SK(F, MT)                                                                                  \
   hipLaunchKernelGGL((gemm_skinny_kernel<F, MT>), g, dim3(SK_THREADS), 0, st, Ah, 2 * lda, (size_t)lda, W.h, \
@@ -807,33 +713,17 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
 #undef TVR_SK_F
 #undef TVR_SK
     } else {
-      PpPlan plan;
-      if (force && force->plan_set)
-        plan = force->plan;
-      else if (m && vec && epi != EPI_STATS)
-        plan = plan_pp_cached(m, M, N, K, a_fmt, epi, a_fmt == ACT_X2F16 && W.x16);
-      if (plan.sk_base >= 0) {
-        if (plan.sk_base > 0)
-          launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, plan.sk_base, true, sl, st, ail);
-        TVR_TRY(launch_pp_sk(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, plan.sk_base,
-                             gemm_pingpong_grid(M, N) - plan.sk_base, plan.sk_blocks, sl, m, st, ail));
-      } else if (plan.ksplit > 1) {
-        TVR_TRY(launch_pp_splitk(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, gemm_pingpong_grid(M, N),
-                                 plan.ksplit, sl, m, st, ail));
-      } else if (plan.tail_base > 0) {
-        launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, plan.tail_base, true, sl, st, ail);
-        TVR_TRY(launch_pp_splitk(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, plan.tail_base,
-                                 gemm_pingpong_grid(M, N) - plan.tail_base, plan.tail_split, sl, m, st, ail));
-      } else {
-        launch_pp(epi, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale, 0, 0, vec, sl, st, ail);
-      }
+      if (pl.n == 0 || pl.base > 0) launch_pp(pl.whole, Ah, lda, W, ldw, M, N, K, ep, acc_scale, 0, pl.base, st);
+      if (pl.n > 0)
+        TVR_TRY(launch_pp_partial(pl, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale,
+                                  gemm_pingpong_grid(M, N) - pl.base, m, st));
     }
   } else {
     const float* Af = static_cast<const float*>(A);
     unsigned* flag = m ? m->range_flag : range_flag;
     // exact-product fp32 GEMMs of a model whose O + MLP-out K reaches PP_SLICE_MIN_K (6.9B, 12B), or any launch
     // of that K: the sliced accumulation (gemm_f32.hpp SLICE_KT; the small tile holds the second accumulator set)
-    const bool f32_sliced = !W.h && !W.x && (K >= PP_SLICE_MIN_K || (m && m->K2 >= PP_SLICE_MIN_K));
+    const bool f32_sliced = !W.h && !W.x && pp_sliced_rule(K, m ? m->K2 : 0);
     const bool large = gemm_use_large(M, N) && !f32_sliced;
 #define TVR_GEMM_LAUNCH(E, TL)                                                                                    \
   do {                                                                                                            \
@@ -2895,9 +2785,8 @@ int tvr_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t gemm_mode, int32_t fl
       (flags & ~(TVR_PLAN_GELU | TVR_PLAN_MODEL_SLICED | TVR_PLAN_EXACT16)))
     return fail(TVR_ERR_INVALID, "tvr_gemm_plan: bad argument");
   const int fmt = gemm_mode == TVR_GEMM_X2F16 ? ACT_X2F16 : ACT_BF16;
-  if (K % (fmt == ACT_X2F16 ? 32 : 64) != 0) return fail(TVR_ERR_UNSUPPORTED, "tvr_gemm_plan: K not a k-tile multiple");
-  // the same sliced rule as plan_pp_cached / launch_gemm
-  const bool sliced = fmt == ACT_X2F16 && (K >= PP_SLICE_MIN_K || (flags & TVR_PLAN_MODEL_SLICED));
+  if (K % pp_ktile(fmt) != 0) return fail(TVR_ERR_UNSUPPORTED, "tvr_gemm_plan: K not a k-tile multiple");
+  const bool sliced = fmt == ACT_X2F16 && pp_sliced_rule(K, (flags & TVR_PLAN_MODEL_SLICED) ? PP_SLICE_MIN_K : 0);
   const PpPlan p = plan_pp(M, N, K, fmt, (flags & TVR_PLAN_GELU) ? EPI_SPLIT_GELU_ACT : EPI_RESID, sliced,
                            fmt == ACT_X2F16 && (flags & TVR_PLAN_EXACT16));
   out[0] = p.ksplit;
@@ -3025,7 +2914,7 @@ int tvr_gemm_launch(tvr_model* m, const tvr_gemm_args* a, void* stream) {
   if (a->skinny != 0 && a->skinny != 1) return bad("skinny must be 0 or 1");
   const bool x2 = a->fmt != TVR_GEMM_BF16, il = a->fmt == TVR_ACT_X2F16_IL, x16 = a->exact16 != 0;
   if (x16 && !x2) return bad("one exact fp16 weight plane takes an x2f16 activation format");
-  const int M = a->M, N = a->N, K = a->K, ktile = x2 ? 32 : 64;
+  const int M = a->M, N = a->N, K = a->K, ktile = pp_ktile(x2 ? ACT_X2F16 : ACT_BF16);
   if (M <= 0 || N <= 0 || K <= 0) return bad("M, N and K must be positive");
   if (K % ktile != 0) return bad("K must be a multiple of the k-tile (" + std::to_string(ktile) + ")");
   if (!a->A || !a->W || !a->out0) return bad("null A, W or out0");

@@ -1396,4 +1396,102 @@ splitk_sk_reduce_kernel(const float* __restrict__ part, int G, int KT, int tile_
   }
 }
 
+// ---- Host: which instantiations exist, and which arguments pick which ----
+// The engine launches the kernels above only through the selectors below; a new template flag is added here.
+
+// k-tile length of a planar format (PlanarFmt<FMT>::BK)
+inline int pp_ktile(int fmt) { return fmt == ACT_X2F16 ? PlanarFmt<ACT_X2F16>::BK : PlanarFmt<ACT_BF16>::BK; }
+static_assert(PlanarFmt<ACT_F16>::BK == PlanarFmt<ACT_BF16>::BK, "pp_ktile: fp16 and bf16 share a k-tile length");
+
+// The model's rule for the x2f16 sliced accumulation (PP_SLICE_MIN_K; the fp32 GEMMs follow it too): this
+// launch's K, or the K2 = d + d_mlp of the model it belongs to (0: none), reaches the threshold.
+inline bool pp_sliced_rule(int K, int K2) { return K >= PP_SLICE_MIN_K || K2 >= PP_SLICE_MIN_K; }
+
+// One launch form of gemm_pingpong_kernel (VAR 0, WIL false).  fmt: the kernel's FMT (interleaved A is ail, not
+// a format).  Split-K partial launches are the skm = false, EPI_BIAS, vec forms with GemmEpi::k_split set.
+struct PpForm {
+  int epi, fmt;
+  bool vec, skm, sl, wx, ail;
+};
+using PpKernel = void (*)(const uint16_t*, int, size_t, const uint16_t*, int, size_t, float, int, int, int, GemmEpi);
+
+constexpr bool pp_form_exists(int epi, int fmt, bool vec, bool skm, bool sl, bool wx, bool ail) {
+  if (fmt != ACT_X2F16 && (sl || wx || ail)) return false;  // slicing, one weight plane, interleaved A: x2f16 only
+  if (ail && !wx && (epi != EPI_BIAS || skm)) return false;  // interleaved A on two weight planes: the plain launch
+  if (skm) return epi == EPI_BIAS && vec;                    // stream-K writes partial tiles only
+  switch (epi) {
+    case EPI_BIAS: return true;
+    case EPI_SPLIT_GELU_ACT:
+    case EPI_RESID: return fmt != ACT_F16;
+    case EPI_STATS: return fmt != ACT_F16 && vec;  // the LDS epilogue only
+    default: return false;
+  }
+}
+
+// Each run-time flag in turn becomes a template argument (B: VEC, SKM, SL, WX, AIL) ...
+template <int EPI, int FMT, bool VEC, bool SKM, bool SL, bool WX, bool AIL>
+PpKernel pp_kernel_at() {
+  if constexpr (pp_form_exists(EPI, FMT, VEC, SKM, SL, WX, AIL))
+    return gemm_pingpong_kernel<EPI, FMT, VEC, 0, SKM, SL, WX, AIL>;  // the one place the kernel is instantiated
+  else
+    return nullptr;
+}
+template <int EPI, int FMT, bool... B, class... Rest>
+PpKernel pp_kernel_at(bool b, Rest... rest) {
+  return b ? pp_kernel_at<EPI, FMT, B..., true>(rest...) : pp_kernel_at<EPI, FMT, B..., false>(rest...);
+}
+template <int EPI>
+PpKernel pp_kernel_epi(const PpForm& f) {
+  switch (f.fmt) {
+    case ACT_X2F16: return pp_kernel_at<EPI, ACT_X2F16>(f.vec, f.skm, f.sl, f.wx, f.ail);
+    case ACT_BF16: return pp_kernel_at<EPI, ACT_BF16>(f.vec, f.skm, f.sl, f.wx, f.ail);
+    case ACT_F16: return pp_kernel_at<EPI, ACT_F16>(f.vec, f.skm, f.sl, f.wx, f.ail);
+    default: return nullptr;
+  }
+}
+// ... the kernel of a form, nullptr for a form that is not instantiated.  (A template, so that a translation
+// unit that never asks, such as a probe with its own variants, compiles none of them.)
+template <int VAR = 0>
+PpKernel pp_kernel(const PpForm& f) {
+  static_assert(VAR == 0, "the engine's forms run VAR 0");
+  switch (f.epi) {
+    case EPI_BIAS: return pp_kernel_epi<EPI_BIAS>(f);
+    case EPI_SPLIT_GELU_ACT: return pp_kernel_epi<EPI_SPLIT_GELU_ACT>(f);
+    case EPI_RESID: return pp_kernel_epi<EPI_RESID>(f);
+    case EPI_STATS: return pp_kernel_epi<EPI_STATS>(f);
+    default: return nullptr;
+  }
+}
+
+// The reduce kernel after a split-K (SK false) or stream-K (SK true) partial launch: the launch's real epilogue
+// in its output layout.  Interleaved A writes interleaved GELU columns; bf16 and fp16 A both write bf16.
+inline int pp_reduce_fmt(int a_fmt, bool ail) { return ail ? ACT_X2F16I : a_fmt == ACT_X2F16 ? ACT_X2F16 : ACT_BF16; }
+using PpReduceKernel = void (*)(const float*, int, int, int, int, int, GemmEpi);
+using PpSkReduceKernel = void (*)(const float*, int, int, int, int, int, int, GemmEpi);
+template <bool SK, int EPI, int FMT>
+auto pp_reduce_at() {
+  if constexpr (SK)
+    return PpSkReduceKernel(splitk_sk_reduce_kernel<EPI, FMT>);
+  else
+    return PpReduceKernel(splitk_reduce_kernel<EPI, FMT>);
+}
+template <bool SK, int EPI>
+auto pp_reduce_epi(int out_fmt) -> decltype(pp_reduce_at<SK, EPI, ACT_BF16>()) {
+  switch (out_fmt) {
+    case ACT_X2F16I: return pp_reduce_at<SK, EPI, ACT_X2F16I>();
+    case ACT_X2F16: return pp_reduce_at<SK, EPI, ACT_X2F16>();
+    case ACT_BF16: return pp_reduce_at<SK, EPI, ACT_BF16>();
+    default: return nullptr;
+  }
+}
+template <bool SK>
+auto pp_reduce_kernel(int epi, int out_fmt) -> decltype(pp_reduce_at<SK, EPI_BIAS, ACT_BF16>()) {
+  switch (epi) {
+    case EPI_BIAS: return pp_reduce_epi<SK, EPI_BIAS>(out_fmt);
+    case EPI_SPLIT_GELU_ACT: return pp_reduce_epi<SK, EPI_SPLIT_GELU_ACT>(out_fmt);
+    case EPI_RESID: return pp_reduce_epi<SK, EPI_RESID>(out_fmt);
+    default: return nullptr;
+  }
+}
+
 }  // namespace tvr

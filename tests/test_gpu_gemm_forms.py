@@ -1,5 +1,6 @@
-"""``gemm_pingpong_kernel``, its launch forms (``launch_pp``, ``launch_pp_splitk``,
-``launch_pp_sk``, the two reduce kernels) and ``gemm_skinny_kernel`` alone,
+"""``gemm_pingpong_kernel``, its launch forms (``launch_pp``, ``launch_pp_partial``
+for split-K and stream-K, the two reduce kernels; the kernels picked by
+``pp_kernel`` / ``pp_reduce_kernel``) and ``gemm_skinny_kernel`` alone,
 through ``tvr_gemm_launch``, against the fp64 reference of tests/gemm_cases.py.
 
 The primitive runs ``launch_gemm`` itself on one tiny model (its weights are
