@@ -211,6 +211,26 @@ int tvr_model_set_exact16(tvr_model* model, const tvr_exact16_layer* layers /*[n
  * row of logits, which softmax probabilities and top-k do not see.  Paths that
  * return logits keep the processed W_U.  NULL, NULL detaches. */
 int tvr_model_set_exact16_unembed(tvr_model* model, const uint16_t* wu, const float* gf);
+/* Weight layout of the exact-fp16 GEMMs.  While the exact-fp16 path runs (X2F16
+ * mode, layers bound) the engine keeps its own row-pair-interleaved copy
+ * (tvr_weight_rows_il) of every bound w1, w2 and wu on the current device, and
+ * the one-plane GEMMs read the copies: a staged weight piece is then 8 whole
+ * 128-byte lines instead of 16 half lines.  Same values, same products in the
+ * same order: bitwise the same results.  Cost: +2 bytes per bound parameter
+ * (about 5.3 GB at Pythia-2.8B, 23 GB at 12B); the caller's planes stay bound,
+ * are still read by everything but those GEMMs, and must stay alive.  The
+ * copies are rebuilt on a rebind and freed on a detach, on a change to another
+ * GEMM mode and with the model.  A copy that does not fit is no error: the
+ * model runs on the plain planes and TVR_W_IL_NOMEM is reported here.
+ * TVR_W_LAYOUT=rows in the environment (read by tvr_model_set_exact16 when the
+ * layers are bound) keeps the plain planes everywhere; so do
+ * TVR_ACT_LAYOUT=planar and engine builds without the wide one-plane tile.
+ * Returns a mask of the flags below (0: plain planes everywhere), -1 for a null
+ * model.  (Backward-compatible addition: ABI 11.) */
+#define TVR_W_IL_LAYERS 1  /* w1 / w2 of every layer are read interleaved */
+#define TVR_W_IL_UNEMBED 2 /* wu is read interleaved */
+#define TVR_W_IL_NOMEM 4   /* a copy did not fit: its GEMMs read the plain plane */
+int32_t tvr_model_weight_layout(const tvr_model* model);
 
 /* Clean-run trace: every layer's hook_resid_pre, attn.hook_z and the K/V
  * inputs, the state run_with_cache keeps (scratch2.py:96, scratch.py:132,137). */
@@ -467,6 +487,16 @@ int tvr_gemm_x2f16(const float* A, int32_t lda, const uint16_t* W, int32_t ldw,
 #define TVR_ACT_X2F16_IL 0x12 /* TVR_GEMM_X2F16 | 0x10 */
 int tvr_act_rows(int32_t fmt, const float* a, int32_t lda, uint16_t* out, int32_t rows,
                  int32_t K, uint32_t* range_flag, void* stream);
+/* One fp16 weight plane w [N][K] (K % 32 == 0) in the row-pair-interleaved
+ * layout of the exact-fp16 GEMMs, halves [ceil(N / 2)][K / 32][2][32]: rows
+ * 2 p and 2 p + 1 share pair p, and per pair and 32-column group 64 B of the
+ * even row are followed by 64 B of the odd row (one 128-B line) — element
+ * (n, k) is half (n / 2) * 2 K + (k / 32) * 64 + (n % 2) * 32 + k % 32.  out
+ * holds ceil(N / 2) * 2 K halves; the missing partner row of an odd N is
+ * written as zeros.  The layout tvr_gemm_launch's exact16 = 2 reads.
+ * TVR_ERR_INVALID for a null w / out, N or K <= 0, K % 32 != 0.  Enqueues on
+ * `stream` without synchronising.  (Backward-compatible addition: ABI 11.) */
+int tvr_weight_rows_il(const uint16_t* w, uint16_t* out, int32_t N, int32_t K, void* stream);
 /* The engine's planar GEMM: A in the activation format above (lda logical
  * elements per row, >= K), W planes from tvr_weight_planes (w_scale: the
  * X2F16 scale, 1 for BF16).  fmt = TVR_ACT_X2F16_IL: A in the interleaved
@@ -569,6 +599,10 @@ int tvr_decode_rows(tvr_model* model, const float* rows, int32_t n, const int32_
  *            1: ONE fp16 plane of w * w_scale holding the weights exactly
  *            (x2f16 formats only: two products per slice).  The interleaved
  *            layout with two weight planes runs only the plain bias launch.
+ *            2: as 1 with the plane row-pair interleaved (tvr_weight_rows_il
+ *            with K = ldw: ceil(N / 2) pairs of 2 ldw halves, allocated by the
+ *            caller); fmt TVR_ACT_X2F16_IL only, TVR_ERR_INVALID with any
+ *            other; otherwise validated as 1; bitwise the results of 1.
  *   epi      TVR_EPI_BIAS   out0[r][c] = acc + bias[c]
  *            TVR_EPI_GELU   c < n_split as TVR_EPI_BIAS; else erf-GELU(acc +
  *                           bias) in the activation format (the layout follows
@@ -610,7 +644,8 @@ int tvr_decode_rows(tvr_model* model, const float* rows, int32_t n, const int32_
  * rows, raw with out_rows, n_split outside [0, N], GELU strides too small for
  * the columns (or, with N and every stride a multiple of 4 — the vector
  * epilogue — ld1h, ps1h, n_split not multiples of 8, ld_raw not of 4), exact16
- * with BF16, the interleaved layout with two weight planes and anything but
+ * with BF16, exact16 2 with any fmt but TVR_ACT_X2F16_IL (TVR_ERR_UNSUPPORTED
+ * on a build without the wide one-plane tile), the interleaved layout with two weight planes and anything but
  * the plain bias launch, skinny with a forced split, a mirror or another
  * epilogue; a forced split or stream-K without the vector epilogue, form_tile
  * outside the raster of 256 x 256 tiles, a split S < 2 or with fewer than 8

@@ -107,6 +107,8 @@ class CGemmArgs(ctypes.Structure):
 EPI_BIAS, EPI_GELU, EPI_RESID = 0, 1, 2
 FORM_PLAN, FORM_PLAIN, FORM_SPLITK, FORM_TAIL, FORM_STREAMK = 0, 1, 2, 3, 4
 SLICE_MODEL, SLICE_ON, SLICE_OFF = 0, 1, 2
+# include/tvr.h tvr_model_weight_layout: the exact-fp16 GEMMs read engine-owned row-pair-interleaved copies
+W_IL_LAYERS, W_IL_UNEMBED, W_IL_NOMEM = 1, 2, 4
 
 
 class CKernelStats(ctypes.Structure):
@@ -171,6 +173,9 @@ SIGNATURES = {
     "tvr_model_set_exact16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "tvr_model_set_exact16_unembed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tvr_model_get_gemm": (ctypes.c_int32, [ctypes.c_void_p]),
+    "tvr_model_weight_layout": (ctypes.c_int32, [ctypes.c_void_p]),
+    "tvr_weight_rows_il": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_void_p]),
     "tvr_split_planes": (ctypes.c_int, [c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "tvr_gemm_x3bf16": (ctypes.c_int, [c_f32p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                        ctypes.c_size_t, c_f32p, c_f32p, ctypes.c_int32, ctypes.c_int32,

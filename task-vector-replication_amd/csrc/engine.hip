@@ -97,8 +97,15 @@ struct MatW {
   size_t wps = 0;
   float wscale = 1.0f;
   bool x16 = false;  // h is ONE plane holding the weights exactly (fp16 values: tvr_model_set_exact16)
+  // x16: the same plane row-pair interleaved (w_layout.hpp), or null.  launch_gemm reads it instead of h where the
+  // launch's form has the interleaved-weight kernel (one-plane wide tile on interleaved A); every other reader
+  // of the plane reads h.
+  const uint16_t* hil = nullptr;
+  // from row elems / ld on.  (A pair of the interleaved copy is two rows long: an even row's pair starts at the
+  // row's own offset.  w_from_row checks the evenness.)
   MatW rows(size_t elems) const {
-    return {f ? f + elems : nullptr, x ? x + elems : nullptr, h ? h + elems : nullptr, wps, wscale, x16};
+    return {f ? f + elems : nullptr, x ? x + elems : nullptr, h ? h + elems : nullptr, wps, wscale, x16,
+            hil ? hil + elems : nullptr};
   }
 };
 
@@ -182,6 +189,16 @@ struct tvr_model {
   // (softmax probability, top-k) do not see; the logits paths keep the processed W_U.
   MatW wux;
   const float* gf = nullptr;
+  // Engine-owned row-pair-interleaved copies (w_layout.hpp) of the bound raw planes, which the one-plane GEMMs on
+  // interleaved activations stage as whole 128-B lines: every layer's W1 and W2 in one allocation, W_U in its own
+  // (+2 B per parameter; the caller's planes stay bound).  Built by sync_w_il whenever the exact-fp16 path is on
+  // in the interleaved activation layout, dropped when it goes off or the binding changes.  w_il_wanted: false
+  // under TVR_W_LAYOUT=rows (read when the layers are bound).  w_il_nomem: a copy did not fit; the model runs on
+  // the plain planes (tvr_model_weight_layout reports it).
+  uint16_t* w_il = nullptr;
+  uint16_t* wu_il = nullptr;
+  bool w_il_wanted = true;
+  bool w_il_nomem = false;
 };
 
 struct tvr_trace {
@@ -353,6 +370,12 @@ bool use_x16(const tvr_model* m) { return m->x16 && m->gemm_mode == TVR_GEMM_X2F
 bool act_layout_interleaved() {
   const char* e = getenv("TVR_ACT_LAYOUT");
   return !(e && std::string(e) == "planar");
+}
+// TVR_W_LAYOUT=rows keeps the exact-fp16 GEMMs on the caller's plain planes: no interleaved copies (A/B runs,
+// tests, fallback)
+bool w_layout_interleaved() {
+  const char* e = getenv("TVR_W_LAYOUT");
+  return !(e && std::string(e) == "rows");
 }
 // Format of the sweep buffers xn, xn2, a2 and xf (Acts::fmt): on the exact-fp16 path the interleaved layout,
 // which only the one-plane GEMM reads; the side buffers (vact, vg, G) keep act_fmt's planar layout.
@@ -593,7 +616,8 @@ int resolve_pp(const PpForm& f, const PpPlan& plan, PpLaunch& pl) {
                                       std::to_string(g.epi) + ", fmt " + std::to_string(g.fmt) + ", vec " +
                                       std::to_string(g.vec) + ", stream-K " + std::to_string(g.skm) + ", sliced " +
                                       std::to_string(g.sl) + ", one weight plane " + std::to_string(g.wx) +
-                                      ", interleaved A " + std::to_string(g.ail));
+                                      ", interleaved A " + std::to_string(g.ail) + ", interleaved W " +
+                                      std::to_string(g.wil));
   };
   pl.skm = plan.sk_base >= 0;
   const bool whole_split = !pl.skm && plan.ksplit > 1, tail_split = !pl.skm && !whole_split && plan.tail_base > 0;
@@ -662,6 +686,11 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
                                      "bf16; K=" + std::to_string(K) + ")");
   // the planar launch's form, plan and kernels, before any event or launch
   const bool wx = a_fmt == ACT_X2F16 && W.x16;  // one exact fp16 weight plane: 2 products per k-step
+  // the plane's row-pair-interleaved copy, where there is one and the launch's form has the kernel for it (the
+  // wide one-plane tile on interleaved A); planar A, the narrow-tile build and the skinny kernel read W.h
+  const bool wil = wx && ail && W.hil != nullptr && pp_wil_available();
+  MatW Wl = W;  // the weight operand as the planar kernels read it
+  if (wil) Wl.h = W.hil;
   bool vec = false, sl = false, skinny = false;
   PpLaunch pl;
   if (planar) {
@@ -684,7 +713,7 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
       else if (m && vec && epi != EPI_STATS)
         plan = plan_pp_cached(m, M, N, K, a_fmt, epi, wx);
       // EPI_STATS has the LDS (vector) epilogue only, whatever planar_epilogue_vec said (N % 4 == 0: above)
-      TVR_TRY(resolve_pp(PpForm{epi, a_fmt, vec || epi == EPI_STATS, false, sl, wx, ail}, plan, pl));
+      TVR_TRY(resolve_pp(PpForm{epi, a_fmt, vec || epi == EPI_STATS, false, sl, wx, ail, wil}, plan, pl));
     }
   }
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -713,9 +742,9 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
 #undef TVR_SK_F
 #undef TVR_SK
     } else {
-      if (pl.n == 0 || pl.base > 0) launch_pp(pl.whole, Ah, lda, W, ldw, M, N, K, ep, acc_scale, 0, pl.base, st);
+      if (pl.n == 0 || pl.base > 0) launch_pp(pl.whole, Ah, lda, Wl, ldw, M, N, K, ep, acc_scale, 0, pl.base, st);
       if (pl.n > 0)
-        TVR_TRY(launch_pp_partial(pl, Ah, lda, a_fmt, W, ldw, M, N, K, ep, acc_scale,
+        TVR_TRY(launch_pp_partial(pl, Ah, lda, a_fmt, Wl, ldw, M, N, K, ep, acc_scale,
                                   gemm_pingpong_grid(M, N) - pl.base, m, st));
     }
   } else {
@@ -772,6 +801,16 @@ int launch_gemm(int epi, const void* A, int lda, int a_fmt, const MatW& W, int l
     m->prof_recs.push_back({ev0, ev1, kind, 2.0 * M * N * (double)K,
                             abytes * M * (double)K + cbytes + wbytes * N * (double)K});
   }
+  return TVR_OK;
+}
+
+// W's rows from row r0 on (row stride ld): a launch over a column range of the weights.  The interleaved copy
+// pairs rows, so pair r0 / 2 starts at row r0's own offset only for an even r0 (the engine's offsets are
+// multiples of d_model, a multiple of 32 on the exact-fp16 path: checked here, not assumed).
+int w_from_row(const MatW& W, int r0, int ld, MatW& out) {
+  if (W.hil && (r0 & 1))
+    return fail(TVR_ERR_INTERNAL, "gemm: odd weight row offset " + std::to_string(r0) + " into a row-pair-interleaved plane");
+  out = W.rows((size_t)r0 * ld);
   return TVR_OK;
 }
 
@@ -1188,7 +1227,8 @@ int launch_w1(tvr_model* m, int l, const void* xn, int M, int c0, int N, const G
   const int epi = fmt != ACT_F32 ? EPI_SPLIT_GELU_ACT : EPI_SPLIT_GELU;
   if (xn2) {
     if (!use_x16(m) || !act_is_x2(fmt)) return fail(TVR_ERR_INTERNAL, "launch_w1: gamma-scaled rows off the x16 path");
-    const MatW W = m->w1x[l].rows((size_t)c0 * d);
+    MatW W;
+    TVR_TRY(w_from_row(m->w1x[l], c0, d, W));
     const int qkv_end = 3 * d - c0;  // first column of the launch that reads xn2
     if (qkv_end <= 0)
       return launch_gemm(epi, xn2, d, fmt, W, d, M, N, d, ep, st, m);
@@ -1211,7 +1251,9 @@ int launch_w1(tvr_model* m, int l, const void* xn, int M, int c0, int N, const G
     if (ep.out0m) e2.out0m = ep.out0m + qkv_end;
     e2.n_split = ep.n_split - qkv_end;
     if (e2.n_split < 0) return fail(TVR_ERR_INTERNAL, "launch_w1: MLP-in columns below the GELU split");
-    return launch_gemm(epi, xn2, d, fmt, W.rows((size_t)qkv_end * d), d, M, N - qkv_end, d, e2, st, m);
+    MatW W2;
+    TVR_TRY(w_from_row(W, qkv_end, d, W2));
+    return launch_gemm(epi, xn2, d, fmt, W2, d, M, N - qkv_end, d, e2, st, m);
   }
   const int nqk = fmt == ACT_BF16 && !m->w1qk.empty() ? std::min(std::max(2 * d - c0, 0), N) : 0;
   if (nqk > 0) {
@@ -1506,9 +1548,97 @@ int tvr_model_create(const tvr_config* cfg, const float* w_embed, const tvr_laye
   return TVR_OK;
 }
 
+// Drop the interleaved weight copies (layers: W1 / W2 of every layer; unembed: W_U).  The caller has made sure
+// that no launch still reads them.
+static void free_w_il(tvr_model* m, bool layers, bool unembed) {
+  if (layers) {
+    if (m->w_il) (void)hipFree(m->w_il);
+    m->w_il = nullptr;
+    for (auto& w : m->w1x) w.hil = nullptr;
+    for (auto& w : m->w2x) w.hil = nullptr;
+  }
+  if (unembed) {
+    if (m->wu_il) (void)hipFree(m->wu_il);
+    m->wu_il = nullptr;
+    m->wux.hil = nullptr;
+  }
+  if (!m->w_il && !m->wu_il) m->w_il_nomem = false;
+}
+
+// Bring the interleaved copies in line with the model's state: present exactly while the exact-fp16 path runs
+// in the interleaved activation layout (the only reader: launch_gemm's wil form) and TVR_W_LAYOUT allowed them
+// at the binding; the unembed's only with its plane bound.  A copy that does not fit is not an error: the
+// GEMMs then read the plain planes (w_il_nomem).  On the null stream, synchronised.
+static int sync_w_il(tvr_model* m) {
+  const bool want = use_x16(m) && m->act_il && m->w_il_wanted && pp_wil_available();
+  if (!want) {
+    if (m->w_il || m->wu_il) TVR_HIP(hipDeviceSynchronize());
+    free_w_il(m, true, true);
+    return TVR_OK;
+  }
+  const tvr_config& c = m->cfg;
+  const int L = c.n_layers, d = c.d_model;
+  const dim3 grid(4096), block(256);
+  bool launched = false;
+  if (!m->w_il) {
+    const size_t n1 = w_il_halves(m->D1, d), n2 = w_il_halves(d, m->K2);
+    if (hipMalloc(&m->w_il, (size_t)L * (n1 + n2) * sizeof(uint16_t)) != hipSuccess) {
+      m->w_il = nullptr;
+      (void)hipGetLastError();
+      m->w_il_nomem = true;
+    } else {
+      uint16_t* p = m->w_il;
+      for (int l = 0; l < L; ++l) {
+        hipLaunchKernelGGL(weight_plane_il_kernel, grid, block, 0, 0, m->w1x[l].h, p, (size_t)m->D1, d);
+        m->w1x[l].hil = p;
+        p += n1;
+        hipLaunchKernelGGL(weight_plane_il_kernel, grid, block, 0, 0, m->w2x[l].h, p, (size_t)d, m->K2);
+        m->w2x[l].hil = p;
+        p += n2;
+      }
+      launched = true;
+    }
+  }
+  if (m->wux.h && !m->wu_il) {
+    if (hipMalloc(&m->wu_il, w_il_halves(c.d_vocab, d) * sizeof(uint16_t)) != hipSuccess) {
+      m->wu_il = nullptr;
+      (void)hipGetLastError();
+      m->w_il_nomem = true;
+    } else {
+      hipLaunchKernelGGL(weight_plane_il_kernel, grid, block, 0, 0, m->wux.h, m->wu_il, (size_t)c.d_vocab, d);
+      m->wux.hil = m->wu_il;
+      launched = true;
+    }
+  }
+  if (launched) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+      free_w_il(m, true, true);
+      return fail(TVR_ERR_HIP, std::string("interleaved weight copies: ") + hipGetErrorString(e));
+    }
+  }
+  return TVR_OK;
+}
+
+int32_t tvr_model_weight_layout(const tvr_model* m) {
+  if (!m) return -1;
+  return (m->w_il ? TVR_W_IL_LAYERS : 0) | (m->wu_il ? TVR_W_IL_UNEMBED : 0) | (m->w_il_nomem ? TVR_W_IL_NOMEM : 0);
+}
+
+int tvr_weight_rows_il(const uint16_t* w, uint16_t* out, int32_t N, int32_t K, void* stream) {
+  if (!w || !out || N <= 0 || K <= 0 || K % 32 != 0) return fail(TVR_ERR_INVALID, "tvr_weight_rows_il: bad argument");
+  const size_t n = w_il_halves(N, K);
+  hipLaunchKernelGGL(weight_plane_il_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0,
+                     (hipStream_t)stream, w, out, (size_t)N, K);
+  TVR_HIP(hipGetLastError());
+  return TVR_OK;
+}
+
 int tvr_model_destroy(tvr_model* m) {
   if (!m) return TVR_OK;
   (void)hipDeviceSynchronize();
+  free_w_il(m, true, true);
   if (m->rot_cos) (void)hipFree(m->rot_cos);
   if (m->rot_sin) (void)hipFree(m->rot_sin);
   if (m->d_w2s) (void)hipFree(m->d_w2s);
@@ -1547,14 +1677,20 @@ static int replan_x2f16(tvr_model* m) {
 int tvr_model_set_exact16_unembed(tvr_model* m, const uint16_t* wu, const float* gf) {
   if (!m) return fail(TVR_ERR_INVALID, "tvr_model_set_exact16_unembed: null model");
   if (!wu != !gf) return fail(TVR_ERR_INVALID, "tvr_model_set_exact16_unembed: give both arrays or neither");
+  if (m->wu_il) TVR_HIP(hipDeviceSynchronize());  // a rebind: no launch may still read the copy about to go
+  free_w_il(m, false, true);
   m->wux = wu ? MatW{nullptr, nullptr, wu, 0, 1.0f, true} : MatW{};
   m->gf = gf;
-  return TVR_OK;
+  return sync_w_il(m);
 }
 
 int tvr_model_set_exact16(tvr_model* m, const tvr_exact16_layer* layers) {
   if (!m) return fail(TVR_ERR_INVALID, "tvr_model_set_exact16: null model");
   const tvr_config& c = m->cfg;
+  // the interleaved copies belong to the planes bound so far: dropped on a rebind and a detach alike (the
+  // re-plan below builds the new binding's)
+  if (m->w_il || m->wu_il) TVR_HIP(hipDeviceSynchronize());
+  free_w_il(m, true, true);
   if (!layers) {
     const bool was = m->x16;
     m->x16 = false;
@@ -1584,6 +1720,7 @@ int tvr_model_set_exact16(tvr_model* m, const tvr_exact16_layer* layers) {
     m->g2.push_back(layers[l].g2);
   }
   m->x16 = true;
+  m->w_il_wanted = w_layout_interleaved();
   return replan_x2f16(m);
 }
 
@@ -1610,6 +1747,7 @@ int tvr_model_set_gemm(tvr_model* m, int32_t mode, void* stream) {
   m->lin_mode = -1;
   m->lin_failed_mode = -1;
   m->gemm_mode = TVR_GEMM_F32;
+  TVR_TRY(sync_w_il(m));  // off the exact-fp16 path: the interleaved weight copies go
   if (mode == TVR_GEMM_F32) return TVR_OK;
 
   const tvr_config& c = m->cfg;
@@ -1729,7 +1867,7 @@ int tvr_model_set_gemm(tvr_model* m, int32_t mode, void* stream) {
   TVR_HIP(hipStreamSynchronize(st));
   m->gemm_mode = mode;
   m->act_il = act_layout_interleaved();
-  return TVR_OK;
+  return sync_w_il(m);  // on the exact-fp16 path in the interleaved layout: the interleaved weight copies
 }
 
 int tvr_model_range_status(tvr_model* m, void* stream) {
@@ -2521,8 +2659,9 @@ static int sweep_block_lin(const SweepCtx& cx, int l, int Rl, const float* cache
       rc = launch_gemm(EPI_BIAS, vg1, d, fmt, m->w1x[l], d, nv, q, d, ex, st, m);
       GemmEpi e2 = ex;
       e2.out0 = ex.out0 + q;
-      if (rc == TVR_OK)
-        rc = launch_gemm(EPI_BIAS, vg2, d, fmt, m->w1x[l].rows((size_t)q * d), d, nv, D1 - q, d, e2, st, m);
+      MatW Wq;
+      if (rc == TVR_OK) rc = w_from_row(m->w1x[l], q, d, Wq);
+      if (rc == TVR_OK) rc = launch_gemm(EPI_BIAS, vg2, d, fmt, Wq, d, nv, D1 - q, d, e2, st, m);
     }
   } else if (nqk > 0) {
     rc = launch_gemm(EPI_BIAS, cx.vact + d, d, ACT_F16, m->w1qk[l], d, nv, nqk, d, eg, st, m);
@@ -2905,7 +3044,12 @@ int tvr_gemm_launch(tvr_model* m, const tvr_gemm_args* a, void* stream) {
   if (!a) return bad("null args");
   if (a->fmt != TVR_GEMM_X2F16 && a->fmt != TVR_ACT_X2F16_IL && a->fmt != TVR_GEMM_BF16)
     return bad("unknown fmt " + std::to_string(a->fmt));
-  if (a->exact16 != 0 && a->exact16 != 1) return bad("exact16 must be 0 or 1");
+  if (a->exact16 < 0 || a->exact16 > 2) return bad("exact16 must be 0, 1 or 2");
+  if (a->exact16 == 2 && a->fmt != TVR_ACT_X2F16_IL)
+    return bad("exact16 must be 0 or 1 with this fmt: the row-pair-interleaved weight plane (2) takes the "
+               "interleaved activation layout");
+  if (a->exact16 == 2 && !pp_wil_available())
+    return fail(TVR_ERR_UNSUPPORTED, "tvr_gemm_launch: this build has no interleaved-weight kernel (TVR_PP_WX_WIDE 0)");
   if (a->epi != TVR_EPI_BIAS && a->epi != TVR_EPI_GELU && a->epi != TVR_EPI_RESID)
     return bad("unknown epi " + std::to_string(a->epi));
   if (a->form < TVR_FORM_PLAN || a->form > TVR_FORM_STREAMK) return bad("unknown form " + std::to_string(a->form));
@@ -3048,7 +3192,8 @@ int tvr_gemm_launch(tvr_model* m, const tvr_gemm_args* a, void* stream) {
   if (rc == TVR_OK) {
     const int epi = a->epi == TVR_EPI_BIAS ? EPI_BIAS : a->epi == TVR_EPI_GELU ? EPI_SPLIT_GELU_ACT : EPI_RESID;
     const int afmt = il ? ACT_X2F16I : x2 ? ACT_X2F16 : ACT_BF16;
-    MatW W{nullptr, nullptr, a->W, (size_t)a->wps, x2 ? a->w_scale : 1.0f, x16};
+    // (exact16 2: the caller's plane is the interleaved one; launch_gemm's form for it is checked above)
+    MatW W{nullptr, nullptr, a->W, (size_t)a->wps, x2 ? a->w_scale : 1.0f, x16, a->exact16 == 2 ? a->W : nullptr};
     // (two weight planes in the interleaved layout: launch_gemm takes them without a model only)
     rc = launch_gemm(epi, a->A, a->lda, afmt, W, a->ldw, M, N, K, e, st, il && !x16 ? nullptr : m, nullptr, &force);
     if (rc == TVR_OK) {

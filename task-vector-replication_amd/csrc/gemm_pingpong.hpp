@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "gemm_planar.hpp"
+#include "w_layout.hpp"
 
 namespace tvr {
 
@@ -901,9 +902,10 @@ __device__ __forceinline__ void pp_tile(const uint16_t* __restrict__ A, int lda,
 // two planes of one k-tile in one 128-B line).  An A piece is then 8 rows x 128 B (whole lines) instead of 16
 // rows x 64 B (half lines), and the LDS A image is the bf16 form's: 128-B rows, chunks 0-3 plane 0, 4-7 plane
 // 1, planar_g<8> swizzle on the source address.  Same bytes, piece counts, vmcnt counts, fragments, k order.
-// WIL (x2f16, probe only: tools/gemm_split_probe x2ppwxiw): the weight plane row-pair interleaved, halves
-// [N / 2][K / 32][2][32] (ldw = the plane's row stride K, N even) — a W piece's 16 rows x 64 B are then 8 whole
-// lines; the LDS image is unchanged, only the per-lane source address differs.
+// WIL (x2f16; the engine's exact-fp16 GEMMs, and tools/gemm_split_probe x2ppwxiw): the weight plane row-pair
+// interleaved (w_layout.hpp: halves [ceil(N / 2)][ldw / 32][2][32], ldw = the plain plane's row stride) — a W
+// piece's 16 rows x 64 B are then 8 whole lines; the LDS image is unchanged, only the per-lane source address
+// (w_il_stage_offset, W_IL_KTILE per k-tile) differs.
 template <int EPI, int FMT, bool VEC, int VAR, bool SL, bool TWO = false, bool AIL = false, bool WIL = false>
 __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int lda, size_t aps,
                                            const uint16_t* __restrict__ W, int ldw, float acc_scale, int M, int N,
@@ -967,9 +969,9 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
         src[R][s] = Ab + plane * aps + (size_t)(ep.a_rows ? ep.a_rows[am] : am) * lda + chunk * 8;
         dst[R][s] = plane * PL + trow0 * (AIL ? ABK : BK);
       } else {
-        const int wn = min(n0 + row, N - 1);
+        const int wn = w_tile_row(n0, row, N);
         if constexpr (WIL)
-          src[R][s] = W + (size_t)(wn >> 1) * (2 * ldw) + (wn & 1) * 32 + chunk * 8;
+          src[R][s] = W + w_il_stage_offset(wn, chunk, ldw);
         else
           src[R][s] = W + (size_t)wn * ldw + chunk * 8;
         dst[R][s] = NPL * PL + trow0 * BK;
@@ -979,7 +981,7 @@ __device__ __forceinline__ void pp_tile_wt(const uint16_t* __restrict__ A, int l
   auto stage = [&](int R, int kt) {
     const bool live = kt < nk;
     // (AIL: a k-tile of A is 64 halves; WIL: a k-tile of a W row pair is 64 halves)
-    const int koff = live ? (kbeg + kt) * ((AIL && R < 2) || (WIL && R >= 2) ? 64 : BK) : 0;
+    const int koff = live ? (kbeg + kt) * (AIL && R < 2 ? 64 : WIL && R >= 2 ? W_IL_KTILE : BK) : 0;
     const int boff = (TWO ? kt % 3 : kt & 1) * BUF;
 #pragma unroll
     for (int s = 0; s < (R >= 2 ? WP : 2); ++s) glds16(src[R][s] + koff, lds + (live ? boff + dst[R][s] : DUMMY));
@@ -1407,16 +1409,21 @@ static_assert(PlanarFmt<ACT_F16>::BK == PlanarFmt<ACT_BF16>::BK, "pp_ktile: fp16
 // launch's K, or the K2 = d + d_mlp of the model it belongs to (0: none), reaches the threshold.
 inline bool pp_sliced_rule(int K, int K2) { return K >= PP_SLICE_MIN_K || K2 >= PP_SLICE_MIN_K; }
 
-// One launch form of gemm_pingpong_kernel (VAR 0, WIL false).  fmt: the kernel's FMT (interleaved A is ail, not
-// a format).  Split-K partial launches are the skm = false, EPI_BIAS, vec forms with GemmEpi::k_split set.
+// One launch form of gemm_pingpong_kernel (VAR 0).  fmt: the kernel's FMT (interleaved A is ail, not a format;
+// wil: the one weight plane row-pair interleaved, w_layout.hpp).  Split-K partial launches are the skm = false,
+// EPI_BIAS, vec forms with GemmEpi::k_split set.
 struct PpForm {
   int epi, fmt;
   bool vec, skm, sl, wx, ail;
+  bool wil = false;
 };
 using PpKernel = void (*)(const uint16_t*, int, size_t, const uint16_t*, int, size_t, float, int, int, int, GemmEpi);
 
-constexpr bool pp_form_exists(int epi, int fmt, bool vec, bool skm, bool sl, bool wx, bool ail) {
+// the interleaved weight plane is a form of the wide one-plane tile on interleaved A (pp_tile_any: wide)
+constexpr bool pp_wil_available() { return TVR_PP_WX_WIDE != 0; }
+constexpr bool pp_form_exists(int epi, int fmt, bool vec, bool skm, bool sl, bool wx, bool ail, bool wil = false) {
   if (fmt != ACT_X2F16 && (sl || wx || ail)) return false;  // slicing, one weight plane, interleaved A: x2f16 only
+  if (wil && !(wx && ail && pp_wil_available())) return false;  // the WIL twin of every wide one-plane AIL form
   if (ail && !wx && (epi != EPI_BIAS || skm)) return false;  // interleaved A on two weight planes: the plain launch
   if (skm) return epi == EPI_BIAS && vec;                    // stream-K writes partial tiles only
   switch (epi) {
@@ -1428,11 +1435,11 @@ constexpr bool pp_form_exists(int epi, int fmt, bool vec, bool skm, bool sl, boo
   }
 }
 
-// Each run-time flag in turn becomes a template argument (B: VEC, SKM, SL, WX, AIL) ...
-template <int EPI, int FMT, bool VEC, bool SKM, bool SL, bool WX, bool AIL>
+// Each run-time flag in turn becomes a template argument (B: VEC, SKM, SL, WX, AIL, WIL) ...
+template <int EPI, int FMT, bool VEC, bool SKM, bool SL, bool WX, bool AIL, bool WIL>
 PpKernel pp_kernel_at() {
-  if constexpr (pp_form_exists(EPI, FMT, VEC, SKM, SL, WX, AIL))
-    return gemm_pingpong_kernel<EPI, FMT, VEC, 0, SKM, SL, WX, AIL>;  // the one place the kernel is instantiated
+  if constexpr (pp_form_exists(EPI, FMT, VEC, SKM, SL, WX, AIL, WIL))
+    return gemm_pingpong_kernel<EPI, FMT, VEC, 0, SKM, SL, WX, AIL, WIL>;  // the one place the kernel is instantiated
   else
     return nullptr;
 }
@@ -1443,9 +1450,9 @@ PpKernel pp_kernel_at(bool b, Rest... rest) {
 template <int EPI>
 PpKernel pp_kernel_epi(const PpForm& f) {
   switch (f.fmt) {
-    case ACT_X2F16: return pp_kernel_at<EPI, ACT_X2F16>(f.vec, f.skm, f.sl, f.wx, f.ail);
-    case ACT_BF16: return pp_kernel_at<EPI, ACT_BF16>(f.vec, f.skm, f.sl, f.wx, f.ail);
-    case ACT_F16: return pp_kernel_at<EPI, ACT_F16>(f.vec, f.skm, f.sl, f.wx, f.ail);
+    case ACT_X2F16: return pp_kernel_at<EPI, ACT_X2F16>(f.vec, f.skm, f.sl, f.wx, f.ail, f.wil);
+    case ACT_BF16: return pp_kernel_at<EPI, ACT_BF16>(f.vec, f.skm, f.sl, f.wx, f.ail, f.wil);
+    case ACT_F16: return pp_kernel_at<EPI, ACT_F16>(f.vec, f.skm, f.sl, f.wx, f.ail, f.wil);
     default: return nullptr;
   }
 }

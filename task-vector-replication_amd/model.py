@@ -366,6 +366,14 @@ class Model(TokenizerMixin):
                 self.exact16 = bool(on)
                 self.gemm = _lib.GEMM_NAMES.get(self._lib.tvr_model_get_gemm(self._h), self.gemm)
 
+    @property
+    def weight_layout(self) -> int:
+        """Which exact-fp16 weights the GEMMs read from the engine's row-pair-interleaved copies (include/tvr.h
+        ``tvr_model_weight_layout``): a mask of ``_lib.W_IL_LAYERS`` / ``W_IL_UNEMBED``, with ``W_IL_NOMEM`` when a
+        copy did not fit and its GEMMs read the plain plane; 0 off the exact-fp16 path and under
+        ``TVR_W_LAYOUT=rows``."""
+        return int(self._lib.tvr_model_weight_layout(self._h))
+
     def _fall_back(self, what: str, err: Exception) -> bool:
         """Move to the next GEMM path without the x2f16 range limit after a
         failed range check: exact-fp16 → processed weights (x2f16, 3 products:

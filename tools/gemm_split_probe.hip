@@ -59,15 +59,7 @@ __global__ void split_act_f16_il_kernel(const float* __restrict__ a, uint16_t* _
   }
 }
 
-// one fp16 plane W [N][K] -> row-pair interleaved [N / 2][K / 32][2][32] (N even, K % 32 == 0): the wxiw path
-__global__ void weight_plane_il_kernel(const uint16_t* __restrict__ w, uint16_t* __restrict__ out, size_t N, int K) {
-  const size_t n = N * K;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / K;
-    const int c = (int)(i % K);
-    out[(r >> 1) * 2 * K + (size_t)(c >> 5) * 64 + (r & 1) * 32 + (c & 31)] = w[i];
-  }
-}
+// (the wxiw path's weight plane: weight_plane_il_kernel, csrc/w_layout.hpp through gemm_pingpong.hpp — the engine's)
 
 __global__ void ref64(const float* A, const float* W, const int* rows, int nr, int N, int K, double* out, double* mag) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -124,7 +116,7 @@ int main(int argc, char** argv) {
     if (ail) {
       hipMalloc(&A2I, sizeof(uint16_t) * 2 * (size_t)s.M * s.K);
       hipLaunchKernelGGL(split_act_f16_il_kernel, dim3(8192), dim3(256), 0, 0, A, A2I, (size_t)s.M, s.K);
-      hipMalloc(&W2I, sizeof(uint16_t) * (size_t)s.N * s.K);
+      hipMalloc(&W2I, sizeof(uint16_t) * w_il_halves(s.N, s.K));
       hipLaunchKernelGGL(weight_plane_il_kernel, dim3(8192), dim3(256), 0, 0, W2, W2I, (size_t)s.N, s.K);
     }
 
