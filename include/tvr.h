@@ -92,7 +92,16 @@ enum tvr_site_kind {
    * range); on a filled trace or a deferred clean forward, every GEMM path.
    * TVR_ERR_INVALID for layer, pos or vec out of range or null vectors.
    * (Backward-compatible addition: ABI 11.) */
-  TVR_SITE_SET_RESID_PRE_VEC = 6
+  TVR_SITE_SET_RESID_PRE_VEC = 6,
+  /* Attention knockout of the last token (tvr_patch_sweep_knockout only): for
+   * every member (layer, head) of the site's set and every blocked key j of its
+   * key list, blocks.{layer}.attn.hook_attn_scores[0, head, -1, j] = -inf in one
+   * forward: hook_pattern[0, head, -1, :] is the softmax over the remaining keys
+   * and 0 on the blocked ones, hook_z[0, -1, head] that pattern times V, and
+   * everything downstream follows.  Other heads and other positions are
+   * untouched.  Fields seq and target; layer / head / vec are ignored.
+   * (Backward-compatible addition: ABI 11.) */
+  TVR_SITE_ATTN_KNOCKOUT_LASTPOS = 7
 };
 
 typedef struct tvr_config {
@@ -444,6 +453,46 @@ int tvr_patch_sweep_sets(tvr_model* model, tvr_trace* trace,
                          int32_t* out_topk, int32_t topk, float* out_logits,
                          void* stream);
 
+/* tvr_patch_sweep_sets with attention-knockout sites (Geva et al. 2023; Wang et
+ * al. 2023): cut the edges from a prompt's last position to chosen key
+ * positions in chosen (layer, head) pairs and re-measure the answer.
+ *   set_off, patches  as tvr_patch_sweep_sets.  A site of kind
+ *            TVR_SITE_ATTN_KNOCKOUT_LASTPOS owns patches[set_off[i] .. set_off[i+1])
+ *            as its (layer, head) members; their `vec` is ignored (-1 is fine);
+ *            the same (layer, head) twice is an error.
+ *   key_off  host [n_sites + 1], non-decreasing, key_off[0] >= 0: a kind-7 site
+ *            owns keys[key_off[i] .. key_off[i+1]); every other kind owns an
+ *            empty range (kinds 4 / 5 keep their patches, kinds 0-3 and 6 own
+ *            neither).  Mixed launches are fine.
+ *   keys     host int32 [key_off[n_sites]] (may be NULL when every range is
+ *            empty): per site strictly increasing positions in [0, seq_len - 1],
+ *            fewer than seq_len of them — one key of the last query must remain,
+ *            so the engine never divides by an empty softmax.
+ *   vectors  may be NULL when no site reads one.
+ * A kind-7 site is planned as TVR_SITE_REPLACE_HEADSET_LASTPOS: it enters at its
+ * lowest member layer as a copy of its clean last row and computes that one row
+ * of every later layer against the clean K/V; at each layer where it has members
+ * one launch (attention_knockout_kernel, timed under TVR_HBM_ATTENTION)
+ * recomputes their z slices between the attention and the O + MLP-out GEMM.  A
+ * site with no members or no keys equals TVR_SITE_NONE bit for bit and adds no
+ * launch; a sweep without kind-7 sites enqueues what tvr_patch_sweep_sets does.
+ * Works on a filled trace and on a deferred clean forward, on every GEMM path,
+ * with exact-fp16 weights bound or not.  All arguments are validated before any
+ * device call: TVR_ERR_INVALID for what tvr_patch_sweep_sets refuses, null or
+ * decreasing key_off, null keys with a non-empty range, keys owned by another
+ * kind, a key out of range or out of order, every key blocked;
+ * TVR_ERR_UNSUPPORTED for a model with more than 64 heads (the head mask) or a
+ * sequence whose scores do not fit the kernel's LDS.  Outputs as
+ * tvr_patch_sweep.  tvr_patch_sweep and tvr_patch_sweep_sets reject kind 7
+ * ("unknown kind").  (Backward-compatible addition: ABI 11.) */
+int tvr_patch_sweep_knockout(tvr_model* model, tvr_trace* trace,
+                             const tvr_site* sites, int32_t n_sites,
+                             const int32_t* set_off, const tvr_head_patch* patches,
+                             const int32_t* key_off, const int32_t* keys,
+                             const float* vectors, int32_t n_vectors, float* out_prob,
+                             int32_t* out_topk, int32_t topk, float* out_logits,
+                             void* stream);
+
 /* out[l][h][:] = zsum[l][h*d_head:(h+1)*d_head] @ W_O[l,h]: turns the z-form
  * capture into the hook_result form of scratch2.py:98 (sum over prompts). */
 int tvr_project_heads(tvr_model* model, const float* zsum /*[L][d]*/,
@@ -546,6 +595,35 @@ int tvr_attention(tvr_model* model, int32_t fmt, const float* qkv, const float* 
                   const tvr_attn_seq* seqs, int32_t n_seq, int32_t row_from, int32_t rows,
                   int32_t cache_rows, void* z, float* zf, int32_t zf_last, int32_t zf_rows,
                   const float* cos_t, const float* sin_t, void* stream);
+/* One knockout launch (what a layer of tvr_patch_sweep_knockout applies after
+ * the attention) on a caller's buffers: for every item, the z slices of the
+ * listed heads of sequence `seq`'s LAST row (row0 + n - 1, position p0 + n - 1)
+ * are overwritten with the attention of that query over the keys that are not
+ * blocked.  Nothing else of z is written.
+ *   qkv, cache, seqs, rows, cache_rows, cos_t, sin_t   as tvr_attention (q0 is
+ *          not read); the tables 16-byte aligned when given
+ *   items  host [n_items]: sequence index, head mask (bit h: head h), and the
+ *          range [first_key, first_key + n_keys) of `keys`: strictly increasing
+ *          positions in [0, p0 + n), fewer than p0 + n of them.  An empty range
+ *          recomputes the plain attention of the listed heads; heads = 0 writes
+ *          nothing.  Two items must not list the same head of the same row.
+ *   z      device, 16-byte aligned, in format fmt on tvr_attention's [rows][K2]
+ *          layout
+ * All arguments are validated on the host before any device call:
+ * TVR_ERR_INVALID for a null model / qkv / z / seqs / items, n_seq <= 0,
+ * n_items <= 0, n_keys < 0 or null keys with n_keys > 0, an unknown fmt,
+ * misaligned buffers, one table without the other, every sequence as
+ * tvr_attention checks it, an item whose seq, head mask or key range is out of
+ * range, keys out of range or order, every key blocked, a (row, head) listed
+ * twice; TVR_ERR_UNSUPPORTED for more than 64 heads or scores that do not fit
+ * the LDS.  A test primitive: it copies the tables to a temporary device buffer
+ * and synchronises `stream`.  An x2f16 value with |z| >= 4095 is reported by
+ * tvr_model_range_status.  (Backward-compatible addition: ABI 11.) */
+typedef struct tvr_knockout_item { int32_t seq; uint64_t heads; int32_t first_key, n_keys; } tvr_knockout_item;
+int tvr_attention_knockout(tvr_model* model, int32_t fmt, const float* qkv, const float* cache,
+                           const tvr_attn_seq* seqs, int32_t n_seq, int32_t rows, int32_t cache_rows,
+                           const tvr_knockout_item* items, int32_t n_items, const int32_t* keys,
+                           int32_t n_keys, void* z, const float* cos_t, const float* sin_t, void* stream);
 /* The pattern kernel of tvr_trace_capture_pattern alone, on a caller's buffer
  * (one layer): sequence s is the positions 0 .. qpos[s] at rows row0[s] .. of
  * qkv, its query the row row0[s] + qpos[s].  Only the query row's Q columns and
@@ -778,7 +856,9 @@ enum tvr_hbm_kind {
                            * layer of the head pass W_O once per chunk of 16 sequences + the z and direction rows */
   TVR_HBM_LNPRE = 2,      /* LayerNormPre rows -> GEMM input format */
   TVR_HBM_ATTENTION = 3,  /* attention: fp32 Q/K/V rows in, z out (activation format [+ fp32 hook_z]); and
-                           * tvr_trace_capture_pattern: per layer the Q row + the K rows read, pattern / mass written */
+                           * tvr_trace_capture_pattern: per layer the Q row + the K rows read, pattern / mass written;
+                           * and the knockout launches of tvr_patch_sweep_knockout, one per layer with members: per
+                           * listed head the Q slice + the K and V slices of every key + the z slice, the mask words */
   TVR_HBM_ROW_STATS = 4,  /* softmax target probability / top-k over one logit row per site */
   TVR_HBM_LIN_ENTRY = 5,  /* linearised entry layer of REPLACE_HEAD sites (the vectors' W1 product G and
                            * the K = d_head entry-row GEMM with its combine epilogue): entering rows' outputs

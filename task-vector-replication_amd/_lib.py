@@ -42,6 +42,7 @@ SITE_SET_RESID_PRE_POS = 3
 SITE_REPLACE_HEADSET_ALLPOS = 4  # tvr_patch_sweep_sets only
 SITE_REPLACE_HEADSET_LASTPOS = 5
 SITE_SET_RESID_PRE_VEC = 6  # hook_resid_pre[layer][0, pos] = vectors[vec] (either sweep)
+SITE_ATTN_KNOCKOUT_LASTPOS = 7  # hook_attn_scores[0, head, -1, keys] = -inf (tvr_patch_sweep_knockout only)
 
 c_f32p = ctypes.c_void_p
 c_i32p = ctypes.c_void_p
@@ -86,6 +87,12 @@ class CAttnSeq(ctypes.Structure):
     """Mirror of ``tvr_attn_seq`` (include/tvr.h; the kernels' SeqDesc)."""
     _fields_ = [("row0", ctypes.c_int32), ("n", ctypes.c_int32), ("p0", ctypes.c_int32),
                 ("cache_row", ctypes.c_int32), ("q0", ctypes.c_int32), ("prefix_live", ctypes.c_int32)]
+
+
+class CKnockoutItem(ctypes.Structure):
+    """Mirror of ``tvr_knockout_item`` (include/tvr.h; tvr_attention_knockout, the knockout test primitive)."""
+    _fields_ = [("seq", ctypes.c_int32), ("heads", ctypes.c_uint64), ("first_key", ctypes.c_int32),
+                ("n_keys", ctypes.c_int32)]
 
 
 ACT_X2F16_IL = 0x12  # include/tvr.h TVR_ACT_X2F16_IL
@@ -162,6 +169,13 @@ SIGNATURES = {
     "tvr_patch_sweep_sets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                             c_i32p, ctypes.c_void_p, c_f32p, ctypes.c_int32, c_f32p, c_i32p,
                                             ctypes.c_int32, c_f32p, ctypes.c_void_p]),
+    "tvr_patch_sweep_knockout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                c_i32p, ctypes.c_void_p, c_i32p, c_i32p, c_f32p, ctypes.c_int32,
+                                                c_f32p, c_i32p, ctypes.c_int32, c_f32p, ctypes.c_void_p]),
+    "tvr_attention_knockout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                              ctypes.c_int32, c_i32p, ctypes.c_int32, ctypes.c_void_p, c_f32p, c_f32p,
+                                              ctypes.c_void_p]),
     "tvr_project_heads": (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p]),
     "tvr_gemm_f32": (ctypes.c_int, [c_f32p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p, c_f32p,
                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -229,6 +243,8 @@ OPS_PATH = LIB_PATH.parent / OPS_NAME
 OPS = ("forward_clean", "patch_sweep", "project_heads", "forward_logits")
 # the joint head-set sweep (tvr_patch_sweep_sets), registered by the same extension
 SET_OPS = ("patch_sweep_sets",)
+# the attention-knockout sweep and its kernel alone (tvr_patch_sweep_knockout, tvr_attention_knockout)
+KNOCKOUT_OPS = ("patch_sweep_knockout", "attention_knockout")
 # the grouped residual capture (tvr_trace_capture_resid), registered by the same extension
 RESID_OPS = ("capture_resid",)
 # one query's attention pattern / per-class attention mass per traced sequence (tvr_trace_capture_pattern)

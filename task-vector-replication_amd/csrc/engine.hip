@@ -26,6 +26,7 @@
 #include "gemm_f32.hpp"
 #include "attention_mfma.hpp"
 #include "attention_pattern.hpp"
+#include "attention_knockout.hpp"
 #include "logit_attribution.hpp"
 #include "gemm_pingpong.hpp"
 #include "gemm_skinny.hpp"
@@ -1010,6 +1011,14 @@ struct Acts {
   const float* hs_vectors = nullptr;
   int hs_n = 0, hs_max_rows = 0;
   double hs_bytes = 0.0;  // algorithmic bytes of the launch (profiling)
+  // knockout sites with members at the layer being run (tvr_patch_sweep_knockout): their last rows' z slices
+  // are recomputed from qkv / ko_cache between the attention and apply_headset (apply_knockout); ko_n == 0: none
+  const KnockoutItem* ko_items = nullptr;
+  const uint32_t* ko_masks = nullptr;
+  const SeqDesc* ko_seqs = nullptr;  // the launch's sequence descriptors (the items index them)
+  const float* ko_cache = nullptr;   // the clean K/V of the prefixes, as the attention launch reads it
+  int ko_n = 0, ko_max_keys = 0;
+  double ko_bytes = 0.0;
 };
 
 // z: the z columns of a2 (fp32 or activation format fmt); zf: optional fp32 copy [rows][d].
@@ -1305,6 +1314,56 @@ int apply_headset(tvr_model* m, const Acts& a, hipStream_t st) {
   return TVR_OK;
 }
 
+// Whether one knockout launch fits the kernel (host only): the head mask and the LDS scores.
+int check_knockout(const tvr_config& c, const char* fn, int max_keys) {
+  if (c.n_heads > 64)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": the knockout head mask covers 64 heads");
+  if (!(c.d_head == 16 || c.d_head == 64 || c.d_head == 80 || c.d_head == 128) || c.rotary_dim * 4 != c.d_head)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": the knockout kernel covers d_head 16 / 64 / 80 / 128 with "
+                                                       "rotary_dim = d_head / 4");
+  if (knockout_lds_bytes(c.d_head, max_keys) > 64 * 1024)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": " + std::to_string(max_keys) + " keys do not fit the "
+                                                       "knockout kernel's 64 KiB of LDS scores");
+  return TVR_OK;
+}
+
+// The layer's attention knockouts (attention_knockout.hpp), after the attention has written z and before the
+// head-set patch and the O + MLP-out GEMM: the listed heads' z slices of the items' last rows are recomputed
+// with the blocked keys left out.  One launch, one wave per (item, head); none without items.
+int apply_knockout(tvr_model* m, const Acts& a, hipStream_t st, const float* cos_t = nullptr,
+                   const float* sin_t = nullptr) {
+  if (a.ko_n <= 0) return TVR_OK;
+  const tvr_config& c = m->cfg;
+  const int d = c.d_model, dh = c.d_head;
+  const float* rot_cos = cos_t ? cos_t : m->rot_cos;
+  const float* rot_sin = sin_t ? sin_t : m->rot_sin;
+  const float inv_scale = 1.0f / std::sqrt((float)dh);
+  const size_t lds = knockout_lds_bytes(dh, a.ko_max_keys);
+  const dim3 grid((unsigned)a.ko_n * c.n_heads), block(64);
+  ProfSpan ps(m, st);
+#define TVR_KO(F, DHV)                                                                                              \
+  hipLaunchKernelGGL((attention_knockout_kernel<F, DHV>), grid, block, lds, st, a.qkv, 3 * d, a.ko_cache, 3 * d,    \
+                     a.ko_seqs, a.ko_items, a.ko_masks, c.n_heads, (void*)a.a2, m->K2, m->range_flag, rot_cos,      \
+                     rot_sin, d, inv_scale)
+#define TVR_KO_DH(F)                                                                         \
+  if (dh == 16) { TVR_KO(F, 16); } else if (dh == 64) { TVR_KO(F, 64); }                     \
+  else if (dh == 80) { TVR_KO(F, 80); } else { TVR_KO(F, 128); }
+  if (a.fmt == ACT_X2F16) {
+    TVR_KO_DH(ACT_X2F16);
+  } else if (a.fmt == ACT_X2F16I) {
+    TVR_KO_DH(ACT_X2F16I);
+  } else if (a.fmt == ACT_BF16) {
+    TVR_KO_DH(ACT_BF16);
+  } else {
+    TVR_KO_DH(ACT_F32);
+  }
+#undef TVR_KO_DH
+#undef TVR_KO
+  TVR_HIP(hipGetLastError());
+  ps.done(TVR_HBM_ATTENTION, a.ko_bytes);
+  return TVR_OK;
+}
+
 // zf_last: the fp32 hook_z copy of each sequence's last row only, at row s of zf
 int run_block(tvr_model* m, int l, int R, const SeqDesc* d_seqs, int n_seqs, int maxT,
               Acts& a, float* qkv_out, const float* cache_qkv, float* zf, hipStream_t st, bool zf_last = false,
@@ -1355,6 +1414,7 @@ int run_block_last_rows(tvr_model* m, int l, int R, const SeqDesc* d_seqs, int n
                            row_from));
   ps.done(TVR_HBM_ATTENTION, attention_bytes(d, n_last, R, a.fmt, zf ? std::min(n_last, zf_rows) : 0));
   if (!write_out) return TVR_OK;
+  TVR_TRY(apply_knockout(m, a, st));
   TVR_TRY(apply_headset(m, a, st));  // global row indices, as d_last's (rows the GEMM does not gather are unread)
   GemmEpi e2{};
   e2.bias = w.b2;
@@ -1371,6 +1431,7 @@ int run_block_last_rows(tvr_model* m, int l, int R, const SeqDesc* d_seqs, int n
 int run_block_out(tvr_model* m, int l, int R, Acts& a, hipStream_t st) {
   const int d = m->cfg.d_model;
   const tvr_layer_weights& w = m->layers[l];
+  TVR_TRY(apply_knockout(m, a, st));
   TVR_TRY(apply_headset(m, a, st));
   GemmEpi e2{};
   e2.bias = w.b2;
@@ -2726,9 +2787,12 @@ static int sweep_block_lin(const SweepCtx& cx, int l, int Rl, const float* cache
 
 // The body of tvr_patch_sweep and tvr_patch_sweep_sets.  set_off == nullptr: the plain sweep (kinds 0-3
 // and 6 only); else sites of kinds 4 / 5 own patches[set_off[i], set_off[i + 1]) and the other kinds own nothing.
-// Without set sites every head-set table is empty and no launch is added.
+// Without set sites every head-set table is empty and no launch is added.  key_off != nullptr
+// (tvr_patch_sweep_knockout, with set_off): sites of kind 7 own patches as their members and
+// keys[key_off[i], key_off[i + 1]); without such sites the knockout tables are empty and no launch is added.
 static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32_t n_sites,
-                      const int32_t* set_off, const tvr_head_patch* patches, const float* vectors,
+                      const int32_t* set_off, const tvr_head_patch* patches, const int32_t* key_off,
+                      const int32_t* keys, const float* vectors,
                       int32_t n_vectors, float* out_prob, int32_t* out_topk, int32_t topk, float* out_logits,
                       void* stream) {
   if (!m || !trace || !sites || n_sites <= 0)
@@ -2754,11 +2818,12 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
                        prefix_share_enabled() && (int)trace->tokens.size() >= trace->n_tokens,
                        fused && fmt != ACT_F32 && L >= 3 && lin_entry_enabled(), ENTRY_GROUP, n_vectors,
                        vectors != nullptr, ((uintptr_t)vectors & 15) == 0, fmt == ACT_BF16 ? 2.0 : 4.0,
-                       sites, n_sites, set_off, patches};
+                       sites, n_sites, set_off, patches, key_off, keys};
   SweepPlan p;
   std::string err;
   const int prc = plan_sweep(in, p, err);
   if (prc != TVR_OK) return fail(prc, err);
+  if (!p.ko_items.empty()) TVR_TRY(check_knockout(c, fn, *std::max_element(p.ko_max_keys.begin(), p.ko_max_keys.end())));
   const int Rc = p.Rc, nc = p.nc;
   bool any_lin = !p.lin_mbs.empty();
   if (any_lin) {
@@ -2803,6 +2868,8 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
   const size_t o_egroups = table(p.egroups);
   const size_t o_hs_items = table(p.hs_items);
   const size_t o_hs_patches = table(p.hs_patches);
+  const size_t o_ko_items = table(p.ko_items);
+  const size_t o_ko_masks = table(p.ko_masks);
   const size_t o_resid = cv.take<float>((size_t)RA * d);
   const size_t o_xn = cv.take<float>((size_t)RA * d);
   const size_t o_xn2 = use_x16(m) ? cv.take<float>((size_t)RA * d) : 0;
@@ -2866,6 +2933,15 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
       a.hs_bytes = p.hs_bytes[l];
     }
     const float* cache = fused ? a.qkv : tqkv;
+    a.ko_n = p.ko_beg[l + 1] - p.ko_beg[l];  // this layer's attention knockouts (0 without kind-7 sites)
+    if (a.ko_n > 0) {
+      a.ko_items = (const KnockoutItem*)(base + o_ko_items) + p.ko_beg[l];
+      a.ko_masks = (const uint32_t*)(base + o_ko_masks);
+      a.ko_seqs = cx.seqs;  // (the last layer's table differs in q0 only, which the kernel does not read)
+      a.ko_cache = cache;
+      a.ko_max_keys = p.ko_max_keys[l];
+      a.ko_bytes = p.ko_bytes[l];
+    }
     float* zf = fused ? trace->z + l * tstride : nullptr;  // the clean rows' hook_z (rows < Rc)
     if (p.use_lin[l]) {
       TVR_TRY(sweep_block_lin(cx, l, Rl, cache, zf));
@@ -2899,7 +2975,7 @@ static int sweep_impl(const char* fn, tvr_model* m, tvr_trace* trace, const tvr_
 int tvr_patch_sweep(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32_t n_sites,
                     const float* vectors, int32_t n_vectors, float* out_prob, int32_t* out_topk,
                     int32_t topk, float* out_logits, void* stream) {
-  return sweep_impl("tvr_patch_sweep", m, trace, sites, n_sites, nullptr, nullptr, vectors, n_vectors, out_prob,
+  return sweep_impl("tvr_patch_sweep", m, trace, sites, n_sites, nullptr, nullptr, nullptr, nullptr, vectors, n_vectors, out_prob,
                     out_topk, topk, out_logits, stream);
 }
 
@@ -2915,8 +2991,28 @@ int tvr_patch_sweep_sets(tvr_model* m, tvr_trace* trace, const tvr_site* sites, 
       return fail(TVR_ERR_INVALID, "tvr_patch_sweep_sets: set_off decreases at site " + std::to_string(i));
   if (set_off[n_sites] > set_off[0] && !patches)
     return fail(TVR_ERR_INVALID, "tvr_patch_sweep_sets: patches is null but the sets are not empty");
-  return sweep_impl("tvr_patch_sweep_sets", m, trace, sites, n_sites, set_off, patches, vectors, n_vectors, out_prob,
-                    out_topk, topk, out_logits, stream);
+  return sweep_impl("tvr_patch_sweep_sets", m, trace, sites, n_sites, set_off, patches, nullptr, nullptr, vectors,
+                    n_vectors, out_prob, out_topk, topk, out_logits, stream);
+}
+
+int tvr_patch_sweep_knockout(tvr_model* m, tvr_trace* trace, const tvr_site* sites, int32_t n_sites,
+                             const int32_t* set_off, const tvr_head_patch* patches, const int32_t* key_off,
+                             const int32_t* keys, const float* vectors, int32_t n_vectors, float* out_prob,
+                             int32_t* out_topk, int32_t topk, float* out_logits, void* stream) {
+  const std::string fn = "tvr_patch_sweep_knockout: ";
+  if (!m || !trace || !sites || n_sites <= 0 || !set_off || !key_off) return fail(TVR_ERR_INVALID, fn + "bad argument");
+  if (set_off[0] < 0) return fail(TVR_ERR_INVALID, fn + "set_off[0] is negative");
+  if (key_off[0] < 0) return fail(TVR_ERR_INVALID, fn + "key_off[0] is negative");
+  for (int i = 0; i < n_sites; ++i) {
+    if (set_off[i + 1] < set_off[i]) return fail(TVR_ERR_INVALID, fn + "set_off decreases at site " + std::to_string(i));
+    if (key_off[i + 1] < key_off[i]) return fail(TVR_ERR_INVALID, fn + "key_off decreases at site " + std::to_string(i));
+  }
+  if (set_off[n_sites] > set_off[0] && !patches)
+    return fail(TVR_ERR_INVALID, fn + "patches is null but the sets are not empty");
+  if (key_off[n_sites] > key_off[0] && !keys)
+    return fail(TVR_ERR_INVALID, fn + "keys is null but the key lists are not empty");
+  return sweep_impl("tvr_patch_sweep_knockout", m, trace, sites, n_sites, set_off, patches, key_off, keys, vectors,
+                    n_vectors, out_prob, out_topk, topk, out_logits, stream);
 }
 
 int tvr_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t gemm_mode, int32_t flags, int32_t* out) {
@@ -3269,6 +3365,103 @@ int tvr_attention(tvr_model* m, int32_t fmt, const float* qkv, const float* cach
   e = hipStreamSynchronize(st);
   if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string("tvr_attention: ") + hipGetErrorString(e));
   (void)hipFree(d_seqs);
+  return rc;
+}
+
+int tvr_attention_knockout(tvr_model* m, int32_t fmt, const float* qkv, const float* cache, const tvr_attn_seq* seqs,
+                           int32_t n_seq, int32_t rows, int32_t cache_rows, const tvr_knockout_item* items,
+                           int32_t n_items, const int32_t* keys, int32_t n_keys, void* z, const float* cos_t,
+                           const float* sin_t, void* stream) {
+  // every check on the host, before any device call
+  const char* fn = "tvr_attention_knockout";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!m) return bad("null model");
+  if (!qkv) return bad("null qkv");
+  if (!z) return bad("null z");
+  if (!seqs) return bad("null seqs");
+  if (!items) return bad("null items");
+  if (n_seq <= 0) return bad("n_seq must be positive");
+  if (n_items <= 0) return bad("n_items must be positive");
+  if (n_keys < 0 || (n_keys > 0 && !keys)) return bad("n_keys is negative, or keys is null");
+  if (fmt != 0 && fmt != TVR_GEMM_X2F16 && fmt != TVR_ACT_X2F16_IL && fmt != TVR_GEMM_BF16)
+    return bad("unknown fmt " + std::to_string(fmt));
+  if (fmt == TVR_ACT_X2F16_IL && m->K2 % 32 != 0) return bad("the interleaved format needs K2 % 32 == 0");
+  if (rows <= 0 || cache_rows < 0) return bad("rows must be positive and cache_rows non-negative");
+  if ((cos_t == nullptr) != (sin_t == nullptr)) return bad("cos_t and sin_t must both be given or both be null");
+  if (((uintptr_t)qkv | (uintptr_t)cache | (uintptr_t)z | (uintptr_t)cos_t | (uintptr_t)sin_t) & 15)
+    return bad("qkv, cache, z and the rotary tables must be 16-byte aligned");
+  const tvr_config& c = m->cfg;
+  for (int s = 0; s < n_seq; ++s) {
+    const tvr_attn_seq& q = seqs[s];
+    const std::string at = " (sequence " + std::to_string(s) + ")";
+    if (q.n < 1) return bad("n must be at least 1" + at);
+    if (q.p0 < 0) return bad("p0 is negative" + at);
+    if ((int64_t)q.p0 + q.n > c.n_ctx) return bad("p0 + n exceeds n_ctx" + at);
+    if (q.row0 < 0 || (int64_t)q.row0 + q.n > rows) return bad("rows [row0, row0 + n) outside the qkv buffer" + at);
+    if (q.prefix_live != 0 && q.prefix_live != 1) return bad("prefix_live must be 0 or 1" + at);
+    if (q.p0 > 0) {
+      if (q.cache_row < 0) return bad("cache_row is negative with p0 > 0" + at);
+      if (q.prefix_live == 0 && !cache) return bad("null cache with p0 > 0 and prefix_live 0" + at);
+      if ((int64_t)q.cache_row + q.p0 > (q.prefix_live ? rows : cache_rows))
+        return bad(std::string("prefix rows [cache_row, cache_row + p0) outside the ") +
+                   (q.prefix_live ? "qkv" : "cache") + " buffer" + at);
+    }
+  }
+  if (c.n_heads > 64) return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": the knockout head mask covers 64 heads");
+  std::vector<KnockoutItem> kitems(n_items);
+  std::vector<uint32_t> masks;
+  std::map<int, uint64_t> listed;  // z row -> heads some item writes
+  int max_keys = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const tvr_knockout_item& it = items[i];
+    const std::string at = " (item " + std::to_string(i) + ")";
+    if (it.seq < 0 || it.seq >= n_seq) return bad("seq out of range" + at);
+    if (c.n_heads < 64 && (it.heads >> c.n_heads) != 0) return bad("head mask names a head outside [0, n_heads)" + at);
+    if (it.first_key < 0 || it.n_keys < 0 || (int64_t)it.first_key + it.n_keys > n_keys)
+      return bad("key range outside the list" + at);
+    const int T = seqs[it.seq].p0 + seqs[it.seq].n, zrow = seqs[it.seq].row0 + seqs[it.seq].n - 1;
+    if (it.n_keys >= T) return bad("every key is blocked: one key of the last query must remain" + at);
+    const int mask_off = (int)masks.size();
+    masks.resize(mask_off + (T + 31) / 32, 0u);
+    for (int q = it.first_key; q < it.first_key + it.n_keys; ++q) {
+      if (keys[q] < 0 || keys[q] >= T) return bad("blocked key outside [0, p0 + n)" + at);
+      if (q > it.first_key && keys[q] <= keys[q - 1]) return bad("blocked keys must be strictly increasing" + at);
+      masks[mask_off + keys[q] / 32] |= 1u << (keys[q] % 32);
+    }
+    uint64_t& seen = listed[zrow];
+    if (seen & it.heads) return bad("two items list the same head of one row" + at);
+    seen |= it.heads;
+    kitems[i] = KnockoutItem{it.seq, mask_off, (uint32_t)it.heads, (uint32_t)(it.heads >> 32)};
+    max_keys = std::max(max_keys, T);
+  }
+  TVR_TRY(check_knockout(c, fn, max_keys));
+
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t b_seqs = align_up((size_t)n_seq * sizeof(SeqDesc)), b_items = align_up((size_t)n_items * sizeof(KnockoutItem));
+  char* dbuf = nullptr;
+  if (hipMalloc(&dbuf, b_seqs + b_items + masks.size() * sizeof(uint32_t) + kAlign) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TVR_ERR_NOMEM, std::string(fn) + ": descriptor buffer");
+  }
+  hipError_t e = hipMemcpyAsync(dbuf, seqs, (size_t)n_seq * sizeof(SeqDesc), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(dbuf + b_seqs, kitems.data(), (size_t)n_items * sizeof(KnockoutItem), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(dbuf + b_seqs + b_items, masks.data(), masks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // pageable host memory
+  int rc = e == hipSuccess ? TVR_OK : fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  Acts a{nullptr, nullptr, const_cast<float*>(qkv), (float*)z,
+         fmt == 0 ? ACT_F32 : fmt == TVR_GEMM_X2F16 ? ACT_X2F16 : fmt == TVR_ACT_X2F16_IL ? ACT_X2F16I : ACT_BF16};
+  a.ko_seqs = (const SeqDesc*)dbuf;
+  a.ko_items = (const KnockoutItem*)(dbuf + b_seqs);
+  a.ko_masks = (const uint32_t*)(dbuf + b_seqs + b_items);
+  a.ko_cache = cache;
+  a.ko_n = n_items;
+  a.ko_max_keys = max_keys;
+  if (rc == TVR_OK) rc = apply_knockout(m, a, st, cos_t, sin_t);
+  e = hipStreamSynchronize(st);
+  if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  (void)hipFree(dbuf);
   return rc;
 }
 

@@ -62,4 +62,14 @@ struct HeadsetPatch {
   int32_t vec;  // row of `vectors`
 };
 
+// attention_knockout.hpp: one (site, layer) record.  The last query of sequence `seq` (an index into the
+// launch's SeqDesc table) is recomputed for the heads of the mask with the keys of the bitmask blocked:
+// key j is bit j % 32 of word masks[mask_off + j / 32], ceil(T / 32) words.
+struct KnockoutItem {
+  int32_t seq;
+  int32_t mask_off;
+  uint32_t heads_lo, heads_hi;  // head h: bit h % 32 of heads_lo (h < 32) or heads_hi
+};
+static_assert(sizeof(KnockoutItem) == 16, "KnockoutItem is read as four 32-bit words");
+
 }  // namespace tvr

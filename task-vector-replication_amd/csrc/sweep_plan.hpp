@@ -47,6 +47,10 @@ struct SweepPlanIn {
   int n_sites;
   const int32_t* set_off;  // nullptr: the plain sweep
   const tvr_head_patch* patches;
+  // tvr_patch_sweep_knockout: a site of kind TVR_SITE_ATTN_KNOCKOUT_LASTPOS owns keys[key_off[i], key_off[i + 1]),
+  // the blocked key positions of its last query; nullptr: no knockout tables (kind 7 is then unknown)
+  const int32_t* key_off = nullptr;
+  const int32_t* keys = nullptr;
 };
 
 struct SweepPlan {
@@ -78,6 +82,12 @@ struct SweepPlan {
   std::vector<HeadsetPatch> hs_patches;
   std::vector<int> hs_beg, hs_max_rows;
   std::vector<double> hs_bytes;
+  // Knockout tables (attention_knockout.hpp): per layer, one item per kind-7 site with members there (entry
+  // order); ko_masks: each such site's blocked keys as ceil(T / 32) words, shared by its layers.
+  std::vector<KnockoutItem> ko_items;
+  std::vector<uint32_t> ko_masks;
+  std::vector<int> ko_beg, ko_max_keys;
+  std::vector<double> ko_bytes;
   // Linearised entry layers (lin_entry.hpp), per such layer: the distinct vectors (rows of G), the entering
   // rows grouped by head, m-blocks of <= 64 rows of one head.
   std::vector<char> use_lin;
@@ -101,6 +111,9 @@ namespace plan_detail {
 inline bool is_headset(int kind) {
   return kind == TVR_SITE_REPLACE_HEADSET_ALLPOS || kind == TVR_SITE_REPLACE_HEADSET_LASTPOS;
 }
+inline bool is_knockout(const SweepPlanIn& in, int kind) {
+  return in.key_off && kind == TVR_SITE_ATTN_KNOCKOUT_LASTPOS;
+}
 inline bool vec_ok(const SweepPlanIn& in, int vec) { return in.have_vectors && vec >= 0 && vec < in.n_vectors; }
 
 // One site's entry layer, first position and rows; "" or what is wrong with it.
@@ -109,7 +122,10 @@ inline const char* classify_site(const SweepPlanIn& in, int i, int& entry, int& 
   const int L = in.n_layers, T = in.seq_len[s.seq];
   const bool is_set = is_headset(s.kind);
   if (is_set && !in.set_off) return "head-set kinds (4, 5) go through tvr_patch_sweep_sets";
-  if (in.set_off && !is_set && in.set_off[i + 1] != in.set_off[i]) return "only head-set kinds (4, 5) own patches";
+  const bool is_ko = is_knockout(in, s.kind);
+  if (in.set_off && !is_set && !is_ko && in.set_off[i + 1] != in.set_off[i])
+    return in.key_off ? "only head-set and knockout kinds (4, 5, 7) own patches" : "only head-set kinds (4, 5) own patches";
+  if (in.key_off && !is_ko && in.key_off[i + 1] != in.key_off[i]) return "only the knockout kind (7) owns keys";
   const bool layer_ok = s.layer >= 0 && s.layer < L;
   p0 = T - 1; nrow = 1;  // (the last position only; the all-position cases adjust)
   switch (s.kind) {
@@ -130,6 +146,30 @@ inline const char* classify_site(const SweepPlanIn& in, int i, int& entry, int& 
       std::sort(lh.begin(), lh.end());
       if (std::adjacent_find(lh.begin(), lh.end()) != lh.end()) return "the same (layer, head) twice in one set";
       if (s.kind == TVR_SITE_REPLACE_HEADSET_ALLPOS && entry < L) { p0 = 0; nrow = T; }
+      return "";
+    }
+    case TVR_SITE_ATTN_KNOCKOUT_LASTPOS: {
+      // Knockout site: planned as the last-position head-set kind — it enters at its lowest member layer as a
+      // copy of its clean last row and runs every layer from there; attention_knockout_kernel recomputes the
+      // members' z slices at each layer where it has some.  No members or no keys: TVR_SITE_NONE.
+      if (!is_ko) return "unknown kind";
+      entry = L;
+      std::vector<std::pair<int, int>> lh;
+      for (int q = in.set_off[i]; q < in.set_off[i + 1]; ++q) {
+        const tvr_head_patch& hp = in.patches[q];
+        if (hp.layer < 0 || hp.layer >= L || hp.head < 0 || hp.head >= in.n_heads) return "member layer/head out of range";
+        entry = std::min(entry, (int)hp.layer);
+        lh.emplace_back(hp.layer, hp.head);
+      }
+      std::sort(lh.begin(), lh.end());
+      if (std::adjacent_find(lh.begin(), lh.end()) != lh.end()) return "the same (layer, head) twice in one set";
+      const int k0 = in.key_off[i], k1 = in.key_off[i + 1];
+      for (int q = k0; q < k1; ++q) {
+        if (in.keys[q] < 0 || in.keys[q] >= T) return "blocked key outside [0, seq_len)";
+        if (q > k0 && in.keys[q] <= in.keys[q - 1]) return "blocked keys must be strictly increasing";
+      }
+      if (k1 - k0 >= T) return "every key is blocked: one key of the last query must remain";
+      if (k1 == k0) entry = L;
       return "";
     }
     case TVR_SITE_NONE:
@@ -240,8 +280,8 @@ inline void layout_rows(const SweepPlanIn& in, SweepPlan& p) {
     p.seqs[nc + k] = p.leader[i] >= 0 ? SeqDesc{Rc + p.row0[i], p.nrow[i], p.p0[i], Rc + p.row0[p.leader[i]], 0, 1}
                                       : SeqDesc{Rc + p.row0[i], p.nrow[i], p.p0[i], srow, 0, 0};
     EntryDesc e{};
-    // a head-set site enters as a plain copy of its clean rows (the entry kernel's TVR_SITE_NONE path)
-    e.kind = is_headset(s.kind) ? (int32_t)TVR_SITE_NONE : s.kind;
+    // a head-set or knockout site enters as a plain copy of its clean rows (the entry kernel's TVR_SITE_NONE path)
+    e.kind = is_headset(s.kind) || is_knockout(in, s.kind) ? (int32_t)TVR_SITE_NONE : s.kind;
     e.row0 = Rc + p.row0[i];
     e.n = p.nrow[i];
     e.p0 = p.p0[i];
@@ -310,9 +350,11 @@ inline void build_headsets(const SweepPlanIn& in, SweepPlan& p) {
   if (!in.set_off || in.set_off[n] <= in.set_off[0]) return;
   const double slice = in.d_head * in.hs_slice_bytes;
   std::vector<std::vector<std::pair<int, int>>> by_layer(L);  // (site, patch) in (entry order, list order)
-  for (int k = 0; k < n; ++k)
+  for (int k = 0; k < n; ++k) {
+    if (!is_headset(in.sites[p.order[k]].kind)) continue;  // (a knockout site's members: build_knockouts)
     for (int q = in.set_off[p.order[k]]; q < in.set_off[p.order[k] + 1]; ++q)
       by_layer[in.patches[q].layer].emplace_back(p.order[k], q);
+  }
   for (int l = 0; l < L; ++l) {
     p.hs_beg[l] = (int)p.hs_items.size();
     const auto& bl = by_layer[l];
@@ -328,6 +370,43 @@ inline void build_headsets(const SweepPlanIn& in, SweepPlan& p) {
     }
   }
   p.hs_beg[L] = (int)p.hs_items.size();
+}
+
+// Per layer, one item per knockout site with members there, in entry order; a site's mask words once.
+inline void build_knockouts(const SweepPlanIn& in, SweepPlan& p) {
+  const int L = in.n_layers, n = in.n_sites;
+  p.ko_beg.assign(L + 1, 0);
+  p.ko_max_keys.assign(L, 0);
+  p.ko_bytes.assign(L, 0.0);
+  if (!in.key_off || !in.set_off) return;
+  std::vector<std::vector<KnockoutItem>> by_layer(L);
+  std::vector<std::vector<int>> keys_of(L);  // the items' sequence lengths
+  for (int k = 0; k < n; ++k) {
+    const int i = p.order[k];
+    if (!is_knockout(in, in.sites[i].kind) || p.entry[i] >= L) continue;  // (no members or no keys: entry == L)
+    const int T = in.seq_len[in.sites[i].seq], mask_off = (int)p.ko_masks.size();
+    p.ko_masks.resize(mask_off + (T + 31) / 32, 0u);
+    for (int q = in.key_off[i]; q < in.key_off[i + 1]; ++q)
+      p.ko_masks[mask_off + in.keys[q] / 32] |= 1u << (in.keys[q] % 32);
+    std::map<int, uint64_t> heads;  // layer -> head mask
+    for (int q = in.set_off[i]; q < in.set_off[i + 1]; ++q) heads[in.patches[q].layer] |= 1ull << in.patches[q].head;
+    for (const auto& lh : heads) {
+      by_layer[lh.first].push_back(KnockoutItem{p.nc + k, mask_off, (uint32_t)lh.second, (uint32_t)(lh.second >> 32)});
+      keys_of[lh.first].push_back(T);
+    }
+  }
+  for (int l = 0; l < L; ++l) {
+    p.ko_beg[l] = (int)p.ko_items.size();
+    for (size_t x = 0; x < by_layer[l].size(); ++x) {
+      const KnockoutItem& it = by_layer[l][x];
+      const int T = keys_of[l][x], nh = __builtin_popcountll(((uint64_t)it.heads_hi << 32) | it.heads_lo);
+      p.ko_items.push_back(it);
+      p.ko_max_keys[l] = std::max(p.ko_max_keys[l], T);
+      // per listed head the Q slice, the K and V slices of every key, the z slice written; the mask words
+      p.ko_bytes[l] += (double)nh * in.d_head * (4.0 * (1 + 2 * T) + in.hs_slice_bytes) + 4.0 * ((T + 31) / 32);
+    }
+  }
+  p.ko_beg[L] = (int)p.ko_items.size();
 }
 
 // Layer l in [1, L-2] of a fused sweep whose entering sites are all REPLACE_HEAD computes its entering rows'
@@ -383,6 +462,7 @@ inline int plan_sweep(const SweepPlanIn& in, SweepPlan& p, std::string& err) {
   plan_detail::layout_rows(in, p);
   plan_detail::group_entries(in, p);
   plan_detail::build_headsets(in, p);
+  plan_detail::build_knockouts(in, p);
   plan_detail::build_lin(in, p);
   return TVR_OK;
 }

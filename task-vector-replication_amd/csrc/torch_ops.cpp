@@ -7,6 +7,8 @@
 //   tvr::forward_clean   tvr_forward_clean / _deferred   (scratch2.py:96,143,183)
 //   tvr::patch_sweep     tvr_patch_sweep                 (scratch2.py:122-125,185-194)
 //   tvr::patch_sweep_sets tvr_patch_sweep_sets           (several scratch2.py:188 hooks in one run_with_hooks)
+//   tvr::patch_sweep_knockout tvr_patch_sweep_knockout   (hook_attn_scores[0, h, -1, keys] = -inf hooks in one run)
+//   tvr::attention_knockout tvr_attention_knockout       (the knockout kernel alone, a test primitive)
 //   tvr::project_heads   tvr_project_heads               (scratch2.py:97-98)
 //   tvr::forward_logits  tvr_forward_logits              (scratch.py:143,206,209)
 //   tvr::capture_resid   tvr_trace_capture_resid         (run_with_cache + hook_resid_pre[l][0, pos], summed)
@@ -30,6 +32,7 @@
 
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "tvr.h"
 
@@ -172,6 +175,85 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> patch_sweep_sets(int64_t model, i
                              (int32_t)topk, want_logits ? logits.data_ptr<float>() : nullptr, cur_stream(device)),
         "tvr_patch_sweep_sets");
   return {prob, top, logits};
+}
+
+// patch_sweep_sets with attention-knockout sites (tvr_patch_sweep_knockout).  key_off: CPU int32 [n_sites + 1];
+// keys: CPU int32 [n_keys], the blocked key positions of the kind-7 sites.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> patch_sweep_knockout(
+    int64_t model, int64_t trace, const at::Tensor& sites, const at::Tensor& set_off, const at::Tensor& patches,
+    const at::Tensor& key_off, const at::Tensor& keys, const std::optional<at::Tensor>& vectors, int64_t topk,
+    bool want_prob, bool want_logits, int64_t d_vocab, c10::Device device) {
+  static_assert(sizeof(tvr_site) == 9 * sizeof(int32_t), "tvr_site is 9 int32 fields");
+  static_assert(sizeof(tvr_head_patch) == 3 * sizeof(int32_t), "tvr_head_patch is 3 int32 fields");
+  TORCH_CHECK_VALUE(sites.dim() == 2 && sites.size(1) == 9, "tvr: sites must be [n_sites, 9] int32");
+  const int64_t n = sites.size(0);
+  TORCH_CHECK_VALUE(n > 0, "tvr: no patch sites");
+  TORCH_CHECK_VALUE(trace != 0, "tvr: patch_sweep_knockout needs a trace");
+  TORCH_CHECK_VALUE(set_off.dim() == 1 && set_off.numel() == n + 1, "tvr: set_off must be [n_sites + 1] int32");
+  TORCH_CHECK_VALUE(key_off.dim() == 1 && key_off.numel() == n + 1, "tvr: key_off must be [n_sites + 1] int32");
+  TORCH_CHECK_VALUE(patches.dim() == 2 && patches.size(1) == 3, "tvr: patches must be [n_patches, 3] int32");
+  TORCH_CHECK_VALUE(keys.dim() == 1, "tvr: keys must be [n_keys] int32");
+  const int32_t* off = host_i32(set_off, "set_off");
+  const int32_t* pat = host_i32(patches, "patches");
+  const int32_t* koff = host_i32(key_off, "key_off");
+  const int32_t* kp = host_i32(keys, "keys");
+  // the C ABI trusts the last offsets as the lengths of patches / keys: check them against the tensors here
+  TORCH_CHECK_VALUE(off[0] >= 0 && off[n] <= patches.size(0), "tvr: set_off runs past patches (", off[n], " > ",
+                    patches.size(0), ") or starts below 0");
+  TORCH_CHECK_VALUE(koff[0] >= 0 && koff[n] <= keys.numel(), "tvr: key_off runs past keys (", koff[n], " > ",
+                    keys.numel(), ") or starts below 0");
+  need_gpu(device);
+  DeviceGuard guard(device);
+  const float* vec = in_f32(vectors, device, "vectors");
+  const int32_t nvec = vectors.has_value() ? (int32_t)(vectors->numel() / std::max<int64_t>(vectors->size(-1), 1)) : 0;
+  auto prob = want_prob ? at::empty({n}, f32(device)) : at::empty({0}, f32(device));
+  auto top = at::empty({topk ? n : 0, topk}, at::TensorOptions().dtype(at::kInt).device(device));
+  auto logits = want_logits ? at::empty({n, d_vocab}, f32(device)) : at::empty({0}, f32(device));
+  check(tvr_patch_sweep_knockout(as_model(model), reinterpret_cast<tvr_trace*>(static_cast<intptr_t>(trace)),
+                                 reinterpret_cast<const tvr_site*>(host_i32(sites, "sites")), (int32_t)n, off,
+                                 reinterpret_cast<const tvr_head_patch*>(pat), koff, kp, vec, nvec,
+                                 want_prob ? prob.data_ptr<float>() : nullptr,
+                                 topk ? top.data_ptr<int32_t>() : nullptr, (int32_t)topk,
+                                 want_logits ? logits.data_ptr<float>() : nullptr, cur_stream(device)),
+        "tvr_patch_sweep_knockout");
+  return {prob, top, logits};
+}
+
+// One knockout launch on a caller's buffers (tvr_attention_knockout).  qkv [rows, 3 d] and cache [cache_rows, 3 d]
+// (or None): contiguous fp32 device tensors; seqs: CPU int32 [n_seq, 6] in tvr_attn_seq field order; items: CPU
+// int64 [n_items, 4] rows (seq, head mask, first_key, n_keys); keys: CPU int32 [n_keys]; z: the activation
+// buffer, written in place in format fmt.
+void attention_knockout(int64_t model, int64_t fmt, const at::Tensor& qkv, const std::optional<at::Tensor>& cache,
+                        const at::Tensor& seqs, const at::Tensor& items, const at::Tensor& keys, at::Tensor& z,
+                        const std::optional<at::Tensor>& cos_t, const std::optional<at::Tensor>& sin_t) {
+  static_assert(sizeof(tvr_attn_seq) == 6 * sizeof(int32_t), "tvr_attn_seq is 6 int32 fields");
+  const c10::Device dev = z.device();
+  need_gpu(dev);
+  TORCH_CHECK_VALUE(qkv.dim() == 2 && z.is_contiguous(), "tvr: qkv must be [rows, 3 d] and z contiguous");
+  TORCH_CHECK_VALUE(seqs.dim() == 2 && seqs.size(1) == 6, "tvr: seqs must be [n_seq, 6] int32");
+  TORCH_CHECK_VALUE(items.dim() == 2 && items.size(1) == 4 && items.device().is_cpu() &&
+                        items.scalar_type() == at::kLong && items.is_contiguous(),
+                    "tvr: items must be a contiguous CPU int64 tensor [n_items, 4]");
+  TORCH_CHECK_VALUE(keys.dim() == 1, "tvr: keys must be [n_keys] int32");
+  const int32_t* sq = host_i32(seqs, "seqs");
+  const int32_t* kp = host_i32(keys, "keys");
+  std::vector<tvr_knockout_item> its((size_t)items.size(0));
+  const int64_t* ip = items.data_ptr<int64_t>();
+  for (size_t i = 0; i < its.size(); ++i) {
+    its[i].seq = (int32_t)ip[4 * i];
+    its[i].heads = (uint64_t)ip[4 * i + 1];
+    its[i].first_key = (int32_t)ip[4 * i + 2];
+    its[i].n_keys = (int32_t)ip[4 * i + 3];
+  }
+  DeviceGuard guard(dev);
+  const float* q = in_f32(qkv, dev, "qkv");
+  const float* cp = in_f32(cache, dev, "cache");
+  check(tvr_attention_knockout(as_model(model), (int32_t)fmt, q, cp, reinterpret_cast<const tvr_attn_seq*>(sq),
+                               (int32_t)seqs.size(0), (int32_t)qkv.size(0),
+                               cache.has_value() ? (int32_t)cache->size(0) : 0, its.data(), (int32_t)its.size(), kp,
+                               (int32_t)keys.numel(), z.data_ptr(), in_f32(cos_t, dev, "cos_t"),
+                               in_f32(sin_t, dev, "sin_t"), cur_stream(dev)),
+        "tvr_attention_knockout");
 }
 
 // zsum [L, d] -> [L, H, d]
@@ -369,6 +451,11 @@ TORCH_LIBRARY(tvr, m) {
         "bool want_logits, int d_vocab, Device device) -> (Tensor, Tensor, Tensor)");
   m.def("patch_sweep_sets(int model, int trace, Tensor sites, Tensor set_off, Tensor patches, Tensor? vectors, "
         "int topk, bool want_prob, bool want_logits, int d_vocab, Device device) -> (Tensor, Tensor, Tensor)");
+  m.def("patch_sweep_knockout(int model, int trace, Tensor sites, Tensor set_off, Tensor patches, Tensor key_off, "
+        "Tensor keys, Tensor? vectors, int topk, bool want_prob, bool want_logits, int d_vocab, Device device) "
+        "-> (Tensor, Tensor, Tensor)");
+  m.def("attention_knockout(int model, int fmt, Tensor qkv, Tensor? cache, Tensor seqs, Tensor items, Tensor keys, "
+        "Tensor(a!) z, Tensor? cos_t, Tensor? sin_t) -> ()");
   m.def("project_heads(int model, Tensor zsum, int n_heads) -> Tensor");
   m.def("forward_logits(int model, Tensor? tokens, Tensor? resid, int start_layer, Tensor seq_lens, int d_vocab, "
         "Device device) -> Tensor");
@@ -389,6 +476,8 @@ TORCH_LIBRARY_IMPL(tvr, CompositeExplicitAutograd, m) {
   m.impl("forward_clean", &forward_clean);
   m.impl("patch_sweep", &patch_sweep);
   m.impl("patch_sweep_sets", &patch_sweep_sets);
+  m.impl("patch_sweep_knockout", &patch_sweep_knockout);
+  m.impl("attention_knockout", &attention_knockout);
   m.impl("project_heads", &project_heads);
   m.impl("forward_logits", &forward_logits);
   m.impl("capture_resid", &capture_resid);

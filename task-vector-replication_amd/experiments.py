@@ -41,6 +41,12 @@ logit lens / vocabulary decoding of residual rows and of task / function vectors
   head_logit_attribution, top_attribution_heads, logit_lens_by_layer,
   decode_vectors
 
+and the causal counterpart of the attention profile, attention knockout (Geva et
+al. 2023; Wang et al. 2023): block the last token's attention to chosen keys in
+a window of layers and re-measure the answer, one sweep for prompts x windows:
+
+  attention_knockout_effect, attention_knockout_by_role
+
 Drop-in notes
 * ``model`` is an ``amd.Model`` instead of a HookedTransformer; it must be
   passed (the reference's defaults bind a module-global model).
@@ -861,3 +867,155 @@ def head_ablation_curve(mean_head_activations: torch.Tensor, causal_indirect_eff
             "top": {"dprob": r["dprob"][:nk], "accuracy": r["accuracy"][:nk]},
             "random": {"dprob": r["dprob"][nk:].view(nk, n_random), "accuracy": r["accuracy"][nk:].view(nk, n_random)},
             "clean_prob": r["clean_prob"], "clean_accuracy": r["clean_accuracy"]}
+
+
+# ------------------------------------------------------------ attention knockout
+def _check_knockout(cfg, prompts, n_answers: int, blocked, windows, heads, topk: int):
+    """Argument checks of ``attention_knockout_effect`` (no engine call).
+    Returns (sorted blocked positions per prompt, windows, heads)."""
+    if len(prompts) != n_answers:
+        raise ValueError("Prompt answers must be of the same length as scrambled prompts")
+    if len(blocked) != len(prompts):
+        raise ValueError("blocked must hold one list of key positions per prompt")
+    if len(prompts) == 0:
+        raise ValueError("no prompts")
+    if topk < 1:
+        raise ValueError("topk must be at least 1")
+    wins = [(int(a), int(b)) for a, b in windows]
+    if any(not (0 <= a <= b < cfg.n_layers) for a, b in wins):
+        raise ValueError("every window must be (first_layer, last_layer) with 0 <= first <= last < n_layers")
+    hs = list(range(cfg.n_heads)) if heads is None else [int(h) for h in heads]
+    if any(not 0 <= h < cfg.n_heads for h in hs) or len(set(hs)) != len(hs):
+        raise ValueError("heads must be distinct head indices in [0, n_heads)")
+    keys = []
+    for p, b in zip(prompts, blocked):
+        ks = sorted({int(j) for j in b})
+        if ks and (ks[0] < 0 or ks[-1] >= len(p)):
+            raise ValueError("blocked key position outside the prompt")
+        if len(ks) >= len(p):
+            raise ValueError("blocked removes every key of a prompt: one key of the last token must remain")
+        keys.append(ks)
+    return keys, wins, hs
+
+
+@range_checked
+def attention_knockout_effect(scrambled_prompts, prompt_answers, blocked, windows, model: Model = None,
+                              heads: Optional[Sequence[int]] = None, topk: int = 1) -> dict:
+    """Attention knockout (Geva et al. 2023; Wang et al. 2023): for each prompt
+    ``i`` and each window ``(first_layer, last_layer)`` (inclusive), one forward
+    in which the LAST token cannot attend to the key positions ``blocked[i]`` —
+    ``hook_attn_scores[0, h, -1, j] = -inf`` — in the heads ``heads`` (default:
+    all) of every layer of the window, scoring the first answer token (B3).
+    Prompts and answers as ``calculate_average_causal_indirect_effect``.
+    Returns ``dprob`` [n_windows] (mean over prompts of p_knocked − p_clean,
+    device), ``rel_dprob`` (mean of (p_knocked − p_clean) / p_clean),
+    ``accuracy`` [n_windows] (share of prompts whose answer token is in the
+    knocked top-``topk``), ``clean_prob`` and ``clean_accuracy`` (floats).  The
+    causal counterpart of ``head_attention_profile``.  One clean forward + one
+    sweep per launch-sized group; a prompt with nothing blocked costs a
+    clean re-evaluation."""
+    cfg = model.cfg
+    prompts, answers = normalize_cie_inputs(model, scrambled_prompts, prompt_answers)
+    keys, wins, hs = _check_knockout(cfg, prompts, len(answers), blocked, windows, heads, topk)
+    dev, n_win, n_prompts = model.device, len(wins), len(prompts)
+    dsum = torch.zeros(n_win, device=dev)
+    rsum = torch.zeros(n_win, device=dev)
+    hits = torch.zeros(n_win, device=dev)
+    clean_p = clean_hits = 0.0
+    # one window's members, (layer, head, vec ignored)
+    members = [np.asarray([(l, h, -1) for l in range(a, b + 1) for h in hs], dtype=np.int32).reshape(-1, 3)
+               for a, b in wins]
+    win_chunk = max(1, min(n_win, MAX_SITES_PER_LAUNCH))
+    group = max(1, MAX_SITES_PER_LAUNCH // win_chunk)
+    for a, b in _chunks(n_prompts, group):
+        seqs = [list(map(int, p)) for p in prompts[a:b]]
+        tg = np.asarray(answers[a:b], dtype=np.int32)
+        n = len(seqs)
+        trace = model._sweep_trace(n, sum(len(s) for s in seqs))
+        clean = model.forward_clean(seqs, targets=tg.tolist(), topk=topk, trace=trace, defer=n_win > 0)
+        tgd = torch.as_tensor(tg, device=dev)
+        for wa, wb in _chunks(n_win, win_chunk):
+            m = wb - wa
+            sites = make_sites(n * m)
+            sites["seq"] = np.repeat(np.arange(n, dtype=np.int32), m)
+            sites["kind"] = _lib.SITE_ATTN_KNOCKOUT_LASTPOS
+            sites["target"] = np.repeat(tg, m)
+            sizes = np.tile([len(x) for x in members[wa:wb]], n)
+            off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+            pat = np.tile(np.concatenate(members[wa:wb]), (n, 1))
+            ksizes = np.repeat([len(k) for k in keys[a:b]], m)
+            koff = np.concatenate([[0], np.cumsum(ksizes)]).astype(np.int32)
+            kk = np.asarray([j for k in keys[a:b] for _ in range(m) for j in k], dtype=np.int32)
+            out = model.patch_sweep_knockout(trace, sites, off, pat, koff, kk, topk=topk)
+            p = out["prob"].view(n, m)
+            diff = p - clean["prob"][:, None]
+            dsum[wa:wb] += diff.sum(0)
+            rsum[wa:wb] += (diff / clean["prob"][:, None]).sum(0)
+            hits[wa:wb] += (out["topk"].view(n, m, topk) == tgd[:, None, None]).any(-1).sum(0)
+        # (the deferred clean outputs are written by the group's first sweep; without windows the forward ran at once)
+        clean_p += float(clean["prob"].sum())
+        clean_hits += float((clean["topk"] == tgd[:, None]).any(-1).sum())
+    return {"dprob": dsum / n_prompts, "rel_dprob": rsum / n_prompts, "accuracy": hits / n_prompts,
+            "clean_prob": clean_p / n_prompts, "clean_accuracy": clean_hits / n_prompts}
+
+
+def knockout_role_prompts(model, contexts: Pairs, function_token: str, seperator_token: Optional[str],
+                          num_contexts: int, len_contexts: int):
+    """``sample_icl_prompts_with_roles`` and the first token of each query
+    pair's label: (prompts, roles, answers).  The labels come from a replay of
+    the same shuffles; the global ``random`` ends where the sampler left it."""
+    state = random.getstate()
+    prompts, roles = sample_icl_prompts_with_roles(model, contexts, function_token, seperator_token, num_contexts,
+                                                   len_contexts)
+    end = random.getstate()
+    random.setstate(state)
+    pool, answers = list(contexts), []
+    for _ in range(num_contexts):
+        random.shuffle(pool)
+        answers.append(int(model.tokenizer.encode(pool[len_contexts][1])[0]))
+    random.setstate(end)
+    return prompts, roles, answers
+
+
+@range_checked
+def attention_knockout_by_role(contexts: Pairs, function_token: str, seperator_token: Optional[str] = None,
+                               model: Model = None, num_contexts: int = 64, len_contexts: int = 4,
+                               roles: Sequence[str] = ROLES[:-1], window: Optional[int] = None, stride: int = 1,
+                               topk: int = 1) -> dict:
+    """Does the prediction DEPEND on where the last token looks?  For every
+    role of ``roles`` (names of ``prompts.ROLES``) and every window of
+    ``window`` consecutive layers (default ``max(1, n_layers // 4)``), stepped
+    by ``stride``, block the last token's attention to all tokens of that role
+    in all heads of the window and re-measure the first token of the query
+    pair's label, over ``num_contexts`` prompts of
+    ``sample_icl_prompts_with_roles`` (``head_attention_profile``'s stream).
+    Returns ``roles``, ``windows`` ((first, last) inclusive), ``dprob`` /
+    ``rel_dprob`` / ``accuracy`` [n_roles, n_windows] (device) and
+    ``clean_prob`` / ``clean_accuracy``.  A role a prompt does not contain
+    leaves that prompt unchanged (an empty key list)."""
+    cfg = model.cfg
+    if num_contexts <= 0:
+        raise ValueError("num_contexts must be positive")
+    if len_contexts < 0 or len_contexts >= len(contexts):
+        raise ValueError("len_contexts must be smaller than the number of contexts (demos + one query)")
+    roles = [str(r) for r in roles]
+    if not roles or any(r not in ROLES for r in roles):
+        raise ValueError(f"roles must be names of {ROLES}")
+    window = max(1, cfg.n_layers // 4) if window is None else int(window)
+    if not 1 <= window <= cfg.n_layers or stride < 1:
+        raise ValueError("window must be in [1, n_layers] and stride at least 1")
+    windows = [(a, a + window - 1) for a in range(0, cfg.n_layers - window + 1, stride)]
+    prompts, token_roles, answers = knockout_role_prompts(model, contexts, function_token, seperator_token,
+                                                          num_contexts, len_contexts)
+    out = {"roles": roles, "windows": windows}
+    rows = {"dprob": [], "rel_dprob": [], "accuracy": []}
+    for r in roles:
+        idx = ROLES.index(r)
+        blocked = [[j for j, c in enumerate(tr) if c == idx] for tr in token_roles]
+        res = attention_knockout_effect(prompts, answers, blocked, windows, model=model, topk=topk)
+        for k in rows:
+            rows[k].append(res[k])
+        out["clean_prob"], out["clean_accuracy"] = res["clean_prob"], res["clean_accuracy"]
+    for k in rows:
+        out[k] = torch.stack(rows[k])
+    return out

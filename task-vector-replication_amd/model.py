@@ -568,6 +568,52 @@ class Model(TokenizerMixin):
             out["logits"] = logits
         return out
 
+    def patch_sweep_knockout(self, trace: Trace, sites: np.ndarray, set_off, patches, key_off, keys,
+                             vectors: Optional[torch.Tensor] = None, topk: int = 0, want_prob: bool = True,
+                             return_logits: bool = False) -> Dict[str, torch.Tensor]:
+        """``patch_sweep_sets`` with attention-knockout sites
+        (tvr_patch_sweep_knockout): site ``i`` of kind
+        ``SITE_ATTN_KNOCKOUT_LASTPOS`` sets
+        ``hook_attn_scores[0, head, -1, j] = -inf`` for every ``(layer, head)``
+        of ``patches[set_off[i]:set_off[i+1]]`` (rows ``(layer, head, vec)``,
+        ``vec`` ignored) and every key position ``j`` of
+        ``keys[key_off[i]:key_off[i+1]]`` (strictly increasing, at least one
+        key of the prompt left).  The other kinds own an empty key range and
+        behave as in ``patch_sweep_sets``.  Returns the same dictionary."""
+        sites = np.ascontiguousarray(sites, dtype=SITE_DTYPE)
+        n = int(sites.shape[0])
+        if n == 0:
+            raise ValueError("no patch sites")
+        off = np.ascontiguousarray(set_off, dtype=np.int32).reshape(-1)
+        pat = np.ascontiguousarray(patches, dtype=np.int32).reshape(-1, 3)
+        koff = np.ascontiguousarray(key_off, dtype=np.int32).reshape(-1)
+        kk = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+        if off.shape[0] != n + 1 or koff.shape[0] != n + 1:
+            raise ValueError("set_off and key_off must have n_sites + 1 entries")
+        if off[0] < 0 or np.any(np.diff(off) < 0) or off[-1] > pat.shape[0]:
+            raise ValueError("set_off must be non-decreasing and stay inside patches")
+        if koff[0] < 0 or np.any(np.diff(koff) < 0) or koff[-1] > kk.shape[0]:
+            raise ValueError("key_off must be non-decreasing and stay inside keys")
+        if vectors is not None:
+            if vectors.device != self.device or vectors.dtype != torch.float32:
+                raise ValueError("vectors must be fp32 on the model device")
+            vectors = vectors.reshape(-1, self.cfg.d_model).contiguous()
+        rows = torch.from_numpy(sites.view(np.int32).reshape(n, len(_lib.SITE_FIELDS)))
+        prob, top, logits = self._op("patch_sweep_knockout", self._h.value, trace._h.value, rows,
+                                     torch.from_numpy(off), torch.from_numpy(pat), torch.from_numpy(koff),
+                                     torch.from_numpy(kk), vectors, topk, want_prob, return_logits,
+                                     self.cfg.d_vocab, self.device)
+        self._check_range("tvr_patch_sweep_knockout")
+        trace._pending_out = None
+        out = {}
+        if want_prob:
+            out["prob"] = prob
+        if topk:
+            out["topk"] = top
+        if return_logits:
+            out["logits"] = logits
+        return out
+
     def capture_resid(self, trace: Trace, positions: Optional[Sequence[int]] = None,
                       groups: Optional[Sequence[int]] = None, n_groups: int = 1,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
