@@ -558,6 +558,54 @@ int tvr_gemm_planar(int32_t fmt, const uint16_t* A, int32_t lda, const uint16_t*
 /* TransformerLens LayerNormPre over rows: (x - mean) / sqrt(var + eps) */
 int tvr_lnpre_f32(const float* x, int32_t ldx, float* y, int32_t ldy,
                   int32_t rows, int32_t d, float eps, void* stream);
+/* One LayerNormPre launch exactly as the engine makes it (engine.hip
+ * launch_lnpre: the row in registers for d % 256 == 0 up to 5120, else three
+ * passes), on a caller's buffers, with every option a block or the unembed uses:
+ *   x, ldx, x_rows   device fp32 [x_rows][ldx]; launch row r reads row
+ *            row_idx[r] (row_idx host [rows], copied to a temporary device
+ *            buffer), or row r with row_idx NULL (then rows <= x_rows)
+ *   fmt      0: y is fp32 [rows][ldy]; TVR_GEMM_X2F16, TVR_ACT_X2F16_IL,
+ *            TVR_GEMM_BF16: y is halves [rows][2 ldy] in the format tvr_act_rows
+ *            describes (BF16: plane 1 holds fp16(y), the Q / K operands).  The
+ *            interleaved layout addresses whole 32-column groups: d and ldy
+ *            multiples of 32
+ *   stats    device [rows][2] or NULL: (mean, sqrt(var + eps)) of launch row r
+ *   copy, copy_rows  device [min(rows, copy_rows)][ldx] or NULL: launch rows
+ *            r < copy_rows of x (after the gather) unchanged; copy_rows > rows
+ *            means all rows
+ *   g1, g2, y2  device [d] gammas, or NULL (x2f16 formats only): y = LNPre(x) g1
+ *            and, with g2 and y2 (laid out as y), y2 = LNPre(x) g2; a value with
+ *            |y| >= 4095 is reported by tvr_model_range_status of `model`
+ *   model    may be NULL without g1
+ * All arguments are validated on the host before any device call:
+ * TVR_ERR_INVALID for null args / x / y, an unknown fmt, rows or x_rows <= 0, d,
+ * ldx or ldy not positive multiples of 4, ldx < d or ldy < d, x, y, y2, copy or a
+ * gamma not 16-byte aligned (stats: 8-byte), a row_idx entry outside
+ * [0, x_rows) (rows > x_rows without row_idx), copy_rows < 0 or positive with
+ * a NULL copy, g1 with fmt 0 or BF16 or with a NULL model, y2 without g1 and g2,
+ * g2 without y2, and for TVR_ACT_X2F16_IL d or ldy not a multiple of 32.
+ * A test primitive: it synchronises `stream`.  (Backward-compatible addition: ABI 11.) */
+typedef struct tvr_lnpre_args {
+  int32_t fmt, rows, d, ldx, ldy, x_rows, copy_rows;
+  float eps;
+  const float* x;
+  const int32_t* row_idx;
+  void* y;
+  float* stats;
+  float* copy;
+  const float* g1;
+  const float* g2;
+  void* y2;
+} tvr_lnpre_args;
+int tvr_lnpre_rows(tvr_model* model, const tvr_lnpre_args* args, void* stream);
+/* dst[r] = src[r] - mean(src[r]) over rows of d floats, device [rows][d], as the
+ * engine centres the exact-fp16 path's logits (in place) and trace export: the
+ * float4 kernel where src and dst are 16-byte aligned and d % 4 == 0, else the
+ * element-wise one.  src == dst is allowed.  TVR_ERR_INVALID, before any device
+ * call, for a null or not float-aligned src / dst, rows or d <= 0, or src and dst
+ * overlapping without being equal.  A test primitive: it synchronises `stream`.
+ * (Backward-compatible addition: ABI 11.) */
+int tvr_center_rows(const float* src, float* dst, int32_t rows, int32_t d, void* stream);
 /* The engine's causal attention of ragged sequences, launched exactly as a
  * block of the model launches it (the kernel form is chosen from the longest
  * p0 + n, TVR_ATT_STAGE / TVR_ATT_VSTAGE / TVR_ROW_ATTN and row_from).

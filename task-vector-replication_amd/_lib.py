@@ -110,6 +110,13 @@ class CGemmArgs(ctypes.Structure):
                     "a_rows", "out_rows")])
 
 
+class CLnpreArgs(ctypes.Structure):
+    """Mirror of ``tvr_lnpre_args`` (include/tvr.h; tvr_lnpre_rows, the LayerNormPre test primitive)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("fmt", "rows", "d", "ldx", "ldy", "x_rows", "copy_rows")] +
+                [("eps", ctypes.c_float)] +
+                [(n, ctypes.c_void_p) for n in ("x", "row_idx", "y", "stats", "copy", "g1", "g2", "y2")])
+
+
 # include/tvr.h enum tvr_gemm_epi / tvr_gemm_form / tvr_gemm_slicing
 EPI_BIAS, EPI_GELU, EPI_RESID = 0, 1, 2
 FORM_PLAN, FORM_PLAIN, FORM_SPLITK, FORM_TAIL, FORM_STREAMK = 0, 1, 2, 3, 4
@@ -182,7 +189,9 @@ SIGNATURES = {
                                     ctypes.c_void_p]),
     "tvr_lnpre_f32": (ctypes.c_int, [c_f32p, ctypes.c_int32, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.c_float, ctypes.c_void_p]),
-    "tvr_workspace_bytes": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "tvr_lnpre_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CLnpreArgs), ctypes.c_void_p]),
+    "tvr_center_rows": (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+    "tvr_workspace_bytes":(ctypes.c_size_t, [ctypes.c_void_p]),
     "tvr_model_set_gemm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "tvr_model_set_exact16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "tvr_model_set_exact16_unembed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -941,6 +941,20 @@ int ensure_lin(tvr_model* m, hipStream_t st) {
   return TVR_OK;
 }
 
+// dst[r] = src[r] - mean(src[r]) over rows of d floats (src == dst allowed): center_rows_kernel's float4 form
+// where both pointers are 16-byte aligned and d % 4 == 0, else the element-wise one (a caller's offset view)
+int launch_center_rows(const float* src, float* dst, int rows, int d, hipStream_t st) {
+  if (rows <= 0) return TVR_OK;
+  const bool v4 = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0 && d % 4 == 0;
+  const dim3 grid((rows + 3) / 4), block(256);
+  if (v4)
+    hipLaunchKernelGGL(center_rows_kernel<true>, grid, block, 0, st, src, dst, rows, d);
+  else
+    hipLaunchKernelGGL(center_rows_kernel<false>, grid, block, 0, st, src, dst, rows, d);
+  TVR_HIP(hipGetLastError());
+  return TVR_OK;
+}
+
 // y: fp32 [rows][ldy] (ACT_F32) or a planar activation format
 // copy: rows < copy_rows of x also go there unchanged (same stride; a fused
 // sweep's clean rows into the trace's hook_resid_pre)
@@ -953,6 +967,9 @@ int launch_lnpre(const float* x, int ldx, const int32_t* idx, void* y, int ldy, 
   ProfSpan ps(m, st);
   if (d % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0)
     return fail(TVR_ERR_UNSUPPORTED, "lnpre: d and strides must be multiples of 4");
+  // act_col / act_ps address whole 32-column groups: plane 1 of a partial last group would lie past the row
+  if (fmt == ACT_X2F16I && (d % 32 != 0 || ldy % 32 != 0))
+    return fail(TVR_ERR_UNSUPPORTED, "lnpre: the interleaved layout needs d and ldy to be multiples of 32");
   if (g1 && (!act_is_x2(fmt) || (y2 && !g2) || !m))
     return fail(TVR_ERR_INTERNAL, "lnpre: the gamma-scaled rows are an x2f16 model path");
   const int rows_per_block = 4;
@@ -1509,12 +1526,7 @@ int run_final(tvr_model* m, const float* resid, const int32_t* d_rows, const int
       // TL's W_U' = center_unembed(fold_ln(W_U)): (LNPre(x) o gamma_f) W_U^T + b_U' differs from TL's logits by
       // -LNPre(x) . (the vocab mean of the d-centred rows), one constant per row, and TL's logits have mean 0 over
       // the vocabulary (W_U' and b_U' are centred over it): subtract each row's mean
-      const bool v4 = ((uintptr_t)lg & 15) == 0 && V % 4 == 0;
-      if (v4)
-        hipLaunchKernelGGL(center_rows_kernel<true>, dim3((cn + 3) / 4), dim3(256), 0, st, lg, lg, cn, V);
-      else
-        hipLaunchKernelGGL(center_rows_kernel<false>, dim3((cn + 3) / 4), dim3(256), 0, st, lg, lg, cn, V);
-      TVR_HIP(hipGetLastError());
+      TVR_TRY(launch_center_rows(lg, lg, cn, V, st));
     }
     ProfSpan ps(m, st);
     hipLaunchKernelGGL(row_stats_kernel, dim3(cn), dim3(STATS_THREADS), 0, st, lg, V, V,
@@ -2057,15 +2069,7 @@ int tvr_trace_read(const tvr_trace* t, int32_t what, int32_t layer, float* dst, 
     // TL's residual stream is centred (every write to it is: W_E, W_O, W_out, their biases); the x16 path's
     // differs from it by one constant per row
     // (a caller's dst may be any float*, e.g. an offset view: the float4 form only where it is 16-B aligned)
-    const bool v4 = ((uintptr_t)dst & 15) == 0 && ((uintptr_t)src & 15) == 0 && d % 4 == 0;
-    if (v4)
-      hipLaunchKernelGGL(center_rows_kernel<true>, dim3((t->n_tokens + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                         src, dst, t->n_tokens, d);
-    else
-      hipLaunchKernelGGL(center_rows_kernel<false>, dim3((t->n_tokens + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                         src, dst, t->n_tokens, d);
-    TVR_HIP(hipGetLastError());
-    return TVR_OK;
+    return launch_center_rows(src, dst, t->n_tokens, d, (hipStream_t)stream);
   }
   TVR_HIP(hipMemcpyAsync(dst, src, (size_t)t->n_tokens * d * sizeof(float), hipMemcpyDeviceToDevice,
                          (hipStream_t)stream));
@@ -3307,6 +3311,71 @@ int tvr_lnpre_f32(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t ro
                   void* stream) {
   if (!x || !y || rows < 0 || d <= 0) return fail(TVR_ERR_INVALID, "tvr_lnpre_f32: bad argument");
   return launch_lnpre(x, ldx, nullptr, y, ldy, rows, d, eps, ACT_F32, (hipStream_t)stream);
+}
+
+int tvr_lnpre_rows(tvr_model* m, const tvr_lnpre_args* a, void* stream) {
+  // every check on the host, before any device call: a wrong argument never becomes a device access
+  auto bad = [](const std::string& what) { return fail(TVR_ERR_INVALID, "tvr_lnpre_rows: " + what); };
+  if (!a) return bad("null args");
+  if (!a->x) return bad("null x");
+  if (!a->y) return bad("null y");
+  const int fmt = a->fmt, rows = a->rows, d = a->d;
+  if (fmt != 0 && fmt != TVR_GEMM_X2F16 && fmt != TVR_ACT_X2F16_IL && fmt != TVR_GEMM_BF16)
+    return bad("unknown fmt " + std::to_string(fmt));
+  if (rows <= 0) return bad("rows must be positive");
+  if (d <= 0 || d % 4 != 0 || a->ldx % 4 != 0 || a->ldy % 4 != 0) return bad("d, ldx and ldy must be positive multiples of 4");
+  if (a->ldx < d || a->ldy < d) return bad("ldx and ldy must be at least d");
+  if (fmt == TVR_ACT_X2F16_IL && (d % 32 != 0 || a->ldy % 32 != 0))
+    return bad("the interleaved format needs d and ldy to be multiples of 32");
+  if (((uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->y2 | (uintptr_t)a->copy | (uintptr_t)a->g1 | (uintptr_t)a->g2) & 15)
+    return bad("x, y, y2, copy and the gammas must be 16-byte aligned");
+  if ((uintptr_t)a->stats & 7) return bad("stats must be 8-byte aligned");
+  if (a->x_rows <= 0) return bad("x_rows must be positive");
+  if (a->row_idx) {
+    for (int r = 0; r < rows; ++r)
+      if (a->row_idx[r] < 0 || a->row_idx[r] >= a->x_rows)
+        return bad("row_idx[" + std::to_string(r) + "] outside [0, x_rows)");
+  } else if (rows > a->x_rows) {
+    return bad("rows exceeds x_rows without row_idx");
+  }
+  if (a->copy_rows < 0) return bad("copy_rows is negative");
+  if (a->copy_rows > 0 && !a->copy) return bad("copy_rows given with a null copy");
+  const bool x2 = fmt == TVR_GEMM_X2F16 || fmt == TVR_ACT_X2F16_IL;
+  if (a->g1 && !x2) return bad("the gamma-scaled rows are x2f16 formats only");
+  if (a->g1 && !m) return bad("g1 needs a model (its range flag)");
+  if (a->y2 && (!a->g1 || !a->g2)) return bad("y2 needs g1 and g2");
+  if (a->g2 && !a->y2) return bad("g2 needs y2");
+
+  const int afmt = fmt == 0 ? ACT_F32 : fmt == TVR_GEMM_X2F16 ? ACT_X2F16 : fmt == TVR_ACT_X2F16_IL ? ACT_X2F16I : ACT_BF16;
+  const hipStream_t st = (hipStream_t)stream;
+  int32_t* d_idx = nullptr;
+  int rc = TVR_OK;
+  if (a->row_idx) {
+    if (hipMalloc(&d_idx, (size_t)rows * sizeof(int32_t)) != hipSuccess)
+      return fail(TVR_ERR_NOMEM, "tvr_lnpre_rows: row index buffer");
+    hipError_t e = hipMemcpyAsync(d_idx, a->row_idx, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // row_idx is pageable host memory
+    if (e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string("tvr_lnpre_rows: ") + hipGetErrorString(e));
+  }
+  if (rc == TVR_OK)
+    rc = launch_lnpre(a->x, a->ldx, d_idx, a->y, a->ldy, rows, d, a->eps, afmt, st, m, reinterpret_cast<float2*>(a->stats),
+                      a->copy, a->copy_rows, a->g1, a->g2, a->y2);
+  const hipError_t e = hipStreamSynchronize(st);
+  if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string("tvr_lnpre_rows: ") + hipGetErrorString(e));
+  if (d_idx) (void)hipFree(d_idx);
+  return rc;
+}
+
+int tvr_center_rows(const float* src, float* dst, int32_t rows, int32_t d, void* stream) {
+  auto bad = [](const std::string& what) { return fail(TVR_ERR_INVALID, "tvr_center_rows: " + what); };
+  if (!src || !dst) return bad("null src or dst");
+  if (rows <= 0 || d <= 0) return bad("rows and d must be positive");
+  if (((uintptr_t)src | (uintptr_t)dst) & 3) return bad("src and dst must be float aligned");
+  const size_t n = (size_t)rows * d;
+  if (src != dst && src < dst + n && dst < src + n) return bad("src and dst overlap without being equal");
+  TVR_TRY(launch_center_rows(src, dst, rows, d, (hipStream_t)stream));
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail(TVR_ERR_HIP, "tvr_center_rows: the launch failed");
+  return TVR_OK;
 }
 
 static_assert(sizeof(tvr_attn_seq) == sizeof(SeqDesc), "tvr_attn_seq is SeqDesc");
