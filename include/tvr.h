@@ -338,6 +338,38 @@ int tvr_trace_capture_pattern(tvr_trace* trace, const int32_t* pos, const int32_
  * its sequence, a target or contrast outside [0, d_vocab).  (Backward-compatible addition: ABI 11.) */
 int tvr_trace_logit_attribution(tvr_trace* trace, const int32_t* pos, const int32_t* target,
                                 const int32_t* contrast, float* out_head, float* out_resid, void* stream);
+/* Per-source-token logit attribution of every head at one query position per traced sequence: FROM WHICH KEYS a
+ * head carries the answer's logit, the product of tvr_trace_capture_pattern and tvr_trace_logit_attribution.
+ * b_V is zero in the processed model (the trace's hook_v carries none), so hook_z[q, h] = sum_j p[j] v[j, h] and
+ *   out_src[s][l][h][j] = p_l,h[q, j] * ((v_l[j, h] @ W_O[l][h]) . u_s / sigma_s)     j in [0, q]
+ *   sum over j of out_src[s][l][h][j] = out_head[s][l][h] of tvr_trace_logit_attribution
+ * with q, u_s, sigma_s as tvr_trace_logit_attribution defines them and p the pattern of
+ * tvr_trace_capture_pattern, recomputed with that kernel's arithmetic (the same bits); columns (q, ld) are
+ * written as +0.0.
+ *   pos, target, contrast  host [n_seq]; pos and contrast may be NULL
+ *   cls      host [n_tokens] class id per traced token in [-1, n_classes), or NULL; n_classes in [1, 64] when
+ *            cls is given
+ *   out_src  device [n_seq][L][H][ld] or NULL, ld > the largest q
+ *   out_cls  device [n_seq][L][H][n_classes] or NULL (needs cls): out_cls[s][l][h][c] = sum over keys j <= q of
+ *            sequence s with class c of out_src[s][l][h][j] (a key of class -1 is counted nowhere; a class
+ *            without keys gives +0.0)
+ * Both outputs are written element-wise: float alignment (4 B) suffices.  Three kernels: the direction pass of
+ * tvr_trace_logit_attribution; the G pass of tvr_head_directions (g = dirs W_O, so that
+ * (v_j @ W_O[h]) . dirs = v_j[h] . g); the source kernel of tvr_attention_source over the trace's Q / K / V rows.
+ * The last two run in groups of layers whose [layers][n_seq][d] G buffer stays within 64 MiB of the model's
+ * workspace (one layer at least); the grouping cannot change a bit.  Sums run in a fixed order, no atomics:
+ * out_src[s][l][h][:] depends bit for bit only on sequence s' rows, l and h, not on n_seq, and not on whether
+ * out_cls is requested.  W_O is the processed fp32 tvr_layer_weights.w2 columns [0, d) on every GEMM path.  Runs
+ * a pending deferred clean forward first; everything is enqueued on `stream`.  Timed under TVR_HBM_CAPTURE (the
+ * direction pass, the G pass per group) and TVR_HBM_ATTENTION (the source kernel per group).  All arguments are
+ * validated before any device call: TVR_ERR_INVALID for a null trace or target, an empty trace, both outputs null,
+ * out_cls without cls, n_classes outside [1, 64] with cls given, a class outside [-1, n_classes), a pos outside
+ * [0, seq_len) or at or beyond n_ctx, a target or contrast outside [0, d_vocab), ld <= the largest q with out_src
+ * given.  TVR_ERR_UNSUPPORTED (before any launch) if the longest key range does not fit the kernel's 64 KiB of
+ * LDS.  (Backward-compatible addition: ABI 11.) */
+int tvr_trace_source_attribution(tvr_trace* trace, const int32_t* pos, const int32_t* target, const int32_t* contrast,
+                                 const int32_t* cls, int32_t n_classes, float* out_src, int32_t ld, float* out_cls,
+                                 void* stream);
 /* Logit lens: every layer's residual row at the query position through the final LayerNormPre and the
  * unembedding, out index [s][l], l in [0, L] (l == L: the model's own last-layer distribution at q).
  * Row l of sequence s is gathered from the trace in place.  targets host [n_seq] or NULL; out_prob device
@@ -703,6 +735,37 @@ int tvr_attention_pattern(tvr_model* model, const float* qkv, int32_t rows, cons
  * `stream` without synchronising.  (Backward-compatible addition: ABI 11.) */
 int tvr_head_attribution(tvr_model* model, int32_t layer, const float* z, const float* dirs, int32_t n,
                          float* out, void* stream);
+/* The G pass of tvr_trace_source_attribution alone, on a caller's buffers (one layer): a direction per row
+ * pulled back through W_O into the heads' z coordinates.
+ *   out_g[i][h*dh + k] = sum over c of dirs[i][c] * W_O[layer][c][h*dh + k]      i in [0, n)
+ * so that (z @ W_O[layer][h]) . dirs[i] = z[h*dh .. (h+1)*dh) . out_g[i][h*dh .. (h+1)*dh).  dirs and out_g
+ * device [n][d], 16-byte aligned (else TVR_ERR_INVALID); nothing outside [n][d] is written and no row beyond
+ * n is read.  W_O: the processed fp32 tvr_layer_weights.w2 columns [0, d) on every GEMM path and with
+ * exact-fp16 weights bound, as in tvr_head_attribution.  The bits of out_g[i][col] depend only on row i of
+ * dirs, the layer and the column.  TVR_ERR_INVALID for null arguments, n <= 0, a layer out of range or a
+ * misaligned buffer, before any device call.  Enqueues on `stream` without synchronising.  Timed under
+ * TVR_HBM_CAPTURE.  (Backward-compatible addition: ABI 11.) */
+int tvr_head_directions(tvr_model* model, int32_t layer, const float* dirs, int32_t n, float* out_g, void* stream);
+/* The source kernel of tvr_trace_source_attribution alone, on a caller's buffer (one layer): sequence s is
+ * the positions 0 .. qpos[s] at rows row0[s] .. of qkv, its query the row row0[s] + qpos[s].
+ *   out_src[s][h][j] = p[j] * (V[row0[s] + j][h*dh .. (h+1)*dh) . g[s][h*dh .. (h+1)*dh))     j in [0, qpos[s]]
+ * with p tvr_attention_pattern's pattern (the same bits); columns (qpos[s], ld) are written as +0.0.  Only
+ * the query row's Q columns and the K and V columns of rows [row0, row0 + qpos] are read.
+ *   qkv    device [rows][3 d]: Q | K | V per row, before rotary, 16-byte aligned
+ *   g      device [n_seq][d], 16-byte aligned, required (tvr_head_directions' output for the sequences'
+ *          directions)
+ *   cls    host [rows] (indexed by row) in [-1, n_classes), or NULL
+ *   out_src device [n_seq][H][ld] or NULL; out_cls device [n_seq][H][n_classes] or NULL (needs cls): the
+ *          sums of out_src over the keys of each class; written element-wise (float alignment)
+ *   cos_t, sin_t  device [n_ctx][d_head / 4], 16-byte aligned, or both NULL: the model's own
+ * Argument rules and errors are tvr_attention_pattern's (with out_src / out_cls for out_pattern / out_mass),
+ * and TVR_ERR_INVALID for a null or misaligned g.  TVR_ERR_UNSUPPORTED before any launch if the longest key
+ * range does not fit the kernel's 64 KiB of LDS ((2 d_head + keys) floats).  A test primitive: it copies the
+ * descriptors to a temporary device buffer and synchronises `stream`.
+ * (Backward-compatible addition: ABI 11.) */
+int tvr_attention_source(tvr_model* model, const float* qkv, int32_t rows, const int32_t* row0, const int32_t* qpos,
+                         int32_t n_seq, const float* g, const int32_t* cls, int32_t n_classes, float* out_src,
+                         int32_t ld, float* out_cls, const float* cos_t, const float* sin_t, void* stream);
 /* Vocabulary decoding of any rows (task vectors, function vectors, residual rows): tvr_trace_logit_lens'
  * stage on a caller's buffer.  rows device [n][d], 16-byte aligned; targets host [n] or NULL; out_prob
  * device [n] or NULL; out_topk device [n][topk] or NULL; same rules and errors as tvr_trace_logit_lens, and
@@ -901,12 +964,16 @@ enum tvr_hbm_kind {
   TVR_HBM_CAPTURE = 1,    /* extraction: sum of hook_z at every prompt's last row -> [d] per layer; and
                            * tvr_trace_capture_resid: rows read x (L + 1) x d x 4 + out read and written; and
                            * tvr_trace_logit_attribution / tvr_head_attribution: the direction pass's rows, and per
-                           * layer of the head pass W_O once per chunk of 16 sequences + the z and direction rows */
+                           * layer of the head pass W_O once per chunk of 16 sequences + the z and direction rows;
+                           * and tvr_head_directions / the G pass of tvr_trace_source_attribution: per layer W_O once
+                           * per chunk of 16 rows + the direction rows once per head + G written */
   TVR_HBM_LNPRE = 2,      /* LayerNormPre rows -> GEMM input format */
   TVR_HBM_ATTENTION = 3,  /* attention: fp32 Q/K/V rows in, z out (activation format [+ fp32 hook_z]); and
                            * tvr_trace_capture_pattern: per layer the Q row + the K rows read, pattern / mass written;
                            * and the knockout launches of tvr_patch_sweep_knockout, one per layer with members: per
-                           * listed head the Q slice + the K and V slices of every key + the z slice, the mask words */
+                           * listed head the Q slice + the K and V slices of every key + the z slice, the mask words;
+                           * and the source kernel of tvr_trace_source_attribution: per layer the Q row, the g row and
+                           * the K and V rows read, the source rows / class sums written */
   TVR_HBM_ROW_STATS = 4,  /* softmax target probability / top-k over one logit row per site */
   TVR_HBM_LIN_ENTRY = 5,  /* linearised entry layer of REPLACE_HEAD sites (the vectors' W1 product G and
                            * the K = d_head entry-row GEMM with its combine epilogue): entering rows' outputs

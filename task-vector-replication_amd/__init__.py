@@ -21,7 +21,8 @@ from .experiments import (apply_layered_vectors_to_zero_shot, apply_layered_vect
                           joint_head_patch_effect, logits_to_next_k_tokens, substitute_task,
                           test_component_hypothesis, top_attention_heads, head_logit_attribution,
                           top_attribution_heads, logit_lens_by_layer, decode_vectors, HeadLogitAttribution,
-                          attention_knockout_effect, attention_knockout_by_role)
+                          attention_knockout_effect, attention_knockout_by_role, head_source_attribution,
+                          top_source_heads)
 
 __version__ = "0.1.0"
 SUBMODULES = ("_lib", "config", "tasks", "tokenizer", "weights", "prompts", "model", "experiments",

@@ -238,6 +238,13 @@ SIGNATURES = {
                                        ctypes.c_int32, ctypes.c_void_p]),
     "tvr_trace_logit_lens": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_f32p, c_i32p, ctypes.c_int32,
                                             ctypes.c_void_p]),
+    "tvr_head_directions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p,
+                                           ctypes.c_void_p]),
+    "tvr_attention_source": (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int32, c_i32p, c_i32p, ctypes.c_int32,
+                                            c_f32p, c_i32p, ctypes.c_int32, c_f32p, ctypes.c_int32, c_f32p, c_f32p,
+                                            c_f32p, ctypes.c_void_p]),
+    "tvr_trace_source_attribution": (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, ctypes.c_int32,
+                                                    c_f32p, ctypes.c_int32, c_f32p, ctypes.c_void_p]),
     "tvr_site_entry": (ctypes.c_int, [ctypes.c_void_p, c_i32p, ctypes.c_int32, c_i32p, ctypes.c_int32, c_f32p, c_f32p,
                                       ctypes.c_void_p, ctypes.c_int32, c_i32p, ctypes.c_void_p, c_f32p,
                                       ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int32, c_i32p, c_i32p, c_i32p,
@@ -263,6 +270,8 @@ PATTERN_MAX_CLASSES = 64
 # direct logit attribution and the logit lens / vocabulary decoding (tvr_head_attribution,
 # tvr_trace_logit_attribution, tvr_trace_logit_lens, tvr_decode_rows)
 ATTRIBUTION_OPS = ("head_attribution", "logit_attribution", "logit_lens", "decode_rows")
+# per-source-token logit attribution (tvr_head_directions, tvr_attention_source, tvr_trace_source_attribution)
+SOURCE_OPS = ("head_directions", "attention_source", "source_attribution")
 # the largest top-k of the row statistics (csrc/kernels.hpp STATS_MAX_K)
 STATS_MAX_K = 16
 

@@ -28,6 +28,7 @@
 #include "attention_pattern.hpp"
 #include "attention_knockout.hpp"
 #include "logit_attribution.hpp"
+#include "source_attribution.hpp"
 #include "gemm_pingpong.hpp"
 #include "gemm_skinny.hpp"
 #include "gemm_planar.hpp"
@@ -1177,6 +1178,22 @@ int check_pattern_args(const char* fn, const int32_t* cls, int n_cls, int32_t n_
   return TVR_OK;
 }
 
+// check_pattern_args for tvr_attention_source and tvr_trace_source_attribution: the same rules on out_src / out_cls.
+int check_source_args(const char* fn, const int32_t* cls, int n_cls, int32_t n_classes, const float* out_src,
+                      const float* out_cls) {
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!out_src && !out_cls) return bad("out_src and out_cls are both null");
+  if (out_cls && !cls) return bad("out_cls needs cls");
+  if (cls) {
+    if (n_classes <= 0 || n_classes > PATTERN_MAX_CLASSES)
+      return bad("n_classes must be in [1, " + std::to_string(PATTERN_MAX_CLASSES) + "]");
+    for (int r = 0; r < n_cls; ++r)
+      if (cls[r] < -1 || cls[r] >= n_classes)
+        return bad("class of row " + std::to_string(r) + " outside [-1, n_classes)");
+  }
+  return TVR_OK;
+}
+
 // head_attribution_kernel over n_layers layers from layer0 (logit_attribution.hpp): grid (chunks of 16 rows, H,
 // layers).  z rows: slab lz at z + lz * z_lstride, row d_zrows[i] (null: i).  out[(i * n_layers + lz) * H + h].
 // Timed under TVR_HBM_CAPTURE: per layer W_O as each chunk of 16 rows reads it, the z and direction rows, out.
@@ -1199,6 +1216,71 @@ int launch_head_attribution(tvr_model* m, const char* fn, const float* dirs, int
 #undef TVR_ATTR
   TVR_HIP(hipGetLastError());
   ps.done(TVR_HBM_CAPTURE, 4.0 * n_layers * ((double)chunks * d * d + 2.0 * n * d + (double)n * H));
+  return TVR_OK;
+}
+
+// head_direction_kernel over n_layers layers from layer0 (source_attribution.hpp): out_g[(lz * n + i) * d + col],
+// grid (chunks of 16 rows, H, layers).  Timed under TVR_HBM_CAPTURE with the bytes the blocks request: per
+// layer W_O once per chunk of 16 rows, the direction rows once per head, G written once.
+int launch_head_directions(tvr_model* m, const char* fn, const float* dirs, int n, int layer0, int n_layers,
+                           float* out_g, hipStream_t st) {
+  const tvr_config& c = m->cfg;
+  const int d = c.d_model, dh = c.d_head, H = c.n_heads;
+  const int chunks = (n + ATTR_CHUNK - 1) / ATTR_CHUNK;
+  if (!(dh == 16 || dh == 64 || dh == 80 || dh == 128) || d % 16 != 0)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": the attribution kernel covers d_head 16 / 64 / 80 / 128");
+  if (H > 65535 || n_layers > 65535)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": too many heads or layers for one launch");
+  ProfSpan ps(m, st);
+  const dim3 grid((unsigned)chunks, (unsigned)H, (unsigned)n_layers), block(64 * ATTR_WAVES);
+#define TVR_HDIR(NT)                                                                                              \
+  hipLaunchKernelGGL((head_direction_kernel<NT>), grid, block, 0, st, dirs, n, m->d_w2s, layer0, m->K2, out_g, d)
+  if (dh == 16) { TVR_HDIR(1); } else if (dh == 64) { TVR_HDIR(4); }
+  else if (dh == 80) { TVR_HDIR(5); } else { TVR_HDIR(8); }
+#undef TVR_HDIR
+  TVR_HIP(hipGetLastError());
+  ps.done(TVR_HBM_CAPTURE, 4.0 * n_layers * ((double)chunks * d * d + ((double)H + 1.0) * n * d));
+  return TVR_OK;
+}
+
+// What launch_source refuses, on the host (tvr_trace_source_attribution checks it before any device call).
+int check_source(const tvr_config& c, const char* fn, int n_seq, int n_layers, int max_keys) {
+  const int dh = c.d_head;
+  if (!(dh == 16 || dh == 64 || dh == 80 || dh == 128) || c.rotary_dim * 4 != dh || c.d_model % 16 != 0)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": the source kernel covers d_head 16 / 64 / 80 / 128 with "
+                                                       "rotary_dim = d_head / 4");
+  if (source_lds_bytes(dh, max_keys) > 64 * 1024)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": " + std::to_string(max_keys) + " keys do not fit the "
+                                                       "kernel's 64 KiB of LDS");
+  if ((int64_t)n_seq * c.n_heads > INT_MAX || n_layers > 65535 || c.n_heads > 65535)
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": too many (sequence, head) pairs or layers for one launch");
+  return TVR_OK;
+}
+
+// source_attribution_kernel over n_layers slabs of `qkv` (slab stride layer_stride floats, rows of 3 d floats)
+// and of `g` (slab stride g_lstride floats, rows of d floats): one wave per (sequence, head), the layer on
+// grid.y; slab l writes layer layer0 + l of outputs that hold out_layers layers.  max_keys: the longest
+// qpos + 1 (sizes the LDS).
+int launch_source(tvr_model* m, const char* fn, const float* qkv, size_t layer_stride, int n_layers,
+                  const PatternSeq* d_seqs, int n_seq, int max_keys, const float* g, size_t g_lstride,
+                  const int32_t* d_cls, int n_classes, float* out_src, int ld, float* out_cls, int layer0,
+                  int out_layers, const float* cos_t, const float* sin_t, hipStream_t st) {
+  const tvr_config& c = m->cfg;
+  const int d = c.d_model, dh = c.d_head;
+  TVR_TRY(check_source(c, fn, n_seq, n_layers, max_keys));
+  const size_t lds = source_lds_bytes(dh, max_keys);
+  const float* rot_cos = cos_t ? cos_t : m->rot_cos;
+  const float* rot_sin = sin_t ? sin_t : m->rot_sin;
+  const float inv_scale = 1.0f / std::sqrt((float)dh);
+  const dim3 grid((unsigned)(n_seq * c.n_heads), (unsigned)n_layers), block(64);
+#define TVR_SOURCE(DHV)                                                                                           \
+  hipLaunchKernelGGL((source_attribution_kernel<DHV>), grid, block, lds, st, qkv, layer_stride, 3 * d, d_seqs,     \
+                     c.n_heads, g, g_lstride, d_cls, n_classes, out_src, ld, out_cls, layer0, out_layers, rot_cos, \
+                     rot_sin, d, inv_scale)
+  if (dh == 16) { TVR_SOURCE(16); } else if (dh == 64) { TVR_SOURCE(64); }
+  else if (dh == 80) { TVR_SOURCE(80); } else { TVR_SOURCE(128); }
+#undef TVR_SOURCE
+  TVR_HIP(hipGetLastError());
   return TVR_OK;
 }
 
@@ -2268,6 +2350,101 @@ int tvr_trace_logit_attribution(tvr_trace* t, const int32_t* pos, const int32_t*
     ps.done(TVR_HBM_CAPTURE, 4.0 * n_seq * d * ((contrast ? 4.0 : 3.0) + (out_resid ? 2.0 * (L + 1) : 0.0)));
   }
   if (out_head) TVR_TRY(launch_head_attribution(m, fn, dirs, n_seq, t->z, lstride, d_rows, 0, L, out_head, st));
+  return TVR_OK;
+}
+
+int tvr_head_directions(tvr_model* m, int32_t layer, const float* dirs, int32_t n, float* out_g, void* stream) {
+  const char* fn = "tvr_head_directions";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!m) return bad("null model");
+  if (!dirs || !out_g) return bad("null argument");
+  if (n <= 0) return bad("n must be positive");
+  if (layer < 0 || layer >= m->cfg.n_layers) return bad("layer out of range");
+  if (((uintptr_t)dirs & 15) || ((uintptr_t)out_g & 15)) return bad("dirs and out_g must be 16-byte aligned");
+  return launch_head_directions(m, fn, dirs, n, layer, 1, out_g, (hipStream_t)stream);
+}
+
+int tvr_trace_source_attribution(tvr_trace* t, const int32_t* pos, const int32_t* target, const int32_t* contrast,
+                                 const int32_t* cls, int32_t n_classes, float* out_src, int32_t ld, float* out_cls,
+                                 void* stream) {
+  const char* fn = "tvr_trace_source_attribution";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!t) return bad("null trace");
+  if (!target) return bad("null target");
+  if (t->n_seq <= 0) return bad("trace is empty: run tvr_forward_clean first");
+  TVR_TRY(check_source_args(fn, cls, t->n_tokens, n_classes, out_src, out_cls));
+  tvr_model* m = t->model;
+  const tvr_config& c = m->cfg;
+  const int L = c.n_layers, d = c.d_model, H = c.n_heads, n_seq = t->n_seq;
+  std::vector<int32_t> rows(n_seq), tg(target, target + n_seq), ct;
+  if (contrast) ct.assign(contrast, contrast + n_seq);
+  std::vector<PatternSeq> seqs(n_seq);
+  int max_q = 0;
+  double keys = 0.0;
+  for (int s = 0; s < n_seq; ++s) {
+    const int q = pos ? pos[s] : t->seq_len[s] - 1;
+    if (q < 0 || q >= t->seq_len[s] || q >= c.n_ctx)
+      return bad("pos of sequence " + std::to_string(s) + " out of range");
+    if (tg[s] < 0 || tg[s] >= c.d_vocab) return bad("target of sequence " + std::to_string(s) + " outside [0, d_vocab)");
+    if (contrast && (ct[s] < 0 || ct[s] >= c.d_vocab))
+      return bad("contrast of sequence " + std::to_string(s) + " outside [0, d_vocab)");
+    rows[s] = t->seq_off[s] + q;
+    seqs[s] = PatternSeq{t->seq_off[s], q};
+    max_q = std::max(max_q, q);
+    keys += q + 1;
+  }
+  if (out_src && ld <= max_q) return bad("ld must exceed the largest query position (" + std::to_string(max_q) + ")");
+  // the direction kernel reads whole float4s of the trace, workspace and w_unembed_t rows
+  if (d % 4 != 0 || ((uintptr_t)m->w_unembed_t & 15))
+    return fail(TVR_ERR_UNSUPPORTED, std::string(fn) + ": d_model must be a multiple of 4 and w_unembed_t 16-byte aligned");
+  TVR_TRY(check_source(c, fn, n_seq, L, max_q + 1));
+  // layers per group: the [layers][n_seq][d] G buffer stays within SOURCE_G_CAP_BYTES (one layer at least);
+  // TVR_SOURCE_G_MB overrides the cap in MiB (read per call; 0: one layer per group; the tests compare the bits)
+  const size_t g_layer = (size_t)n_seq * d;
+  const size_t g_cap = (size_t)std::max(0, env_int("TVR_SOURCE_G_MB", (int)(SOURCE_G_CAP_BYTES >> 20))) << 20;
+  const int per_group = (int)std::min<size_t>((size_t)L, std::max<size_t>(1, g_cap / (g_layer * sizeof(float))));
+  hipStream_t st = (hipStream_t)stream;
+  TVR_TRY(flush_pending(t, stream));  // a deferred clean forward runs now (it uses the workspace: carve after it)
+  Carve cv;
+  const size_t o_rows = cv.take<int32_t>(n_seq);
+  const size_t o_tg = cv.take<int32_t>(n_seq);
+  const size_t o_ct = contrast ? cv.take<int32_t>(n_seq) : 0;
+  const size_t o_seqs = cv.take<PatternSeq>(seqs.size());
+  const size_t o_cls = out_cls ? cv.take<int32_t>((size_t)t->n_tokens) : 0;
+  const size_t o_dirs = cv.take<float>(g_layer);
+  const size_t o_g = cv.take<float>(g_layer * per_group);
+  TVR_TRY(ensure_workspace(m, cv.off, st));
+  char* base = m->ws;
+  UploadBatch ub;
+  ub.add(o_rows, rows);
+  ub.add(o_tg, tg);
+  if (contrast) ub.add(o_ct, ct);
+  ub.add(o_seqs, seqs);
+  if (out_cls) ub.add(o_cls, std::vector<int32_t>(cls, cls + t->n_tokens));
+  TVR_TRY(flush_uploads(m, st, base, ub));
+  const size_t lstride = (size_t)t->max_tokens * d;
+  float* dirs = (float*)(base + o_dirs);
+  float* G = (float*)(base + o_g);
+  {
+    ProfSpan ps(m, st);
+    hipLaunchKernelGGL(attr_direction_kernel, dim3((unsigned)n_seq), dim3(64), 0, st, t->resid + L * lstride,
+                       (const int32_t*)(base + o_rows), m->w_unembed_t, (const int32_t*)(base + o_tg),
+                       contrast ? (const int32_t*)(base + o_ct) : nullptr, c.ln_eps, dirs, d);
+    TVR_HIP(hipGetLastError());
+    // the final rows and the unembed rows in, the directions out
+    ps.done(TVR_HBM_CAPTURE, 4.0 * n_seq * d * (contrast ? 4.0 : 3.0));
+  }
+  for (int l0 = 0; l0 < L; l0 += per_group) {
+    const int nl = std::min(per_group, L - l0);
+    TVR_TRY(launch_head_directions(m, fn, dirs, n_seq, l0, nl, G, st));
+    ProfSpan ps(m, st);
+    TVR_TRY(launch_source(m, fn, t->qkv + (size_t)l0 * 3 * lstride, 3 * lstride, nl, (const PatternSeq*)(base + o_seqs),
+                          n_seq, max_q + 1, G, g_layer, out_cls ? (const int32_t*)(base + o_cls) : nullptr, n_classes,
+                          out_src, ld, out_cls, l0, L, nullptr, nullptr, st));
+    // per layer: every sequence's Q row, g row and its K and V rows [0, qpos] in, the source rows and class sums out
+    ps.done(TVR_HBM_ATTENTION, 4.0 * nl * ((2.0 * n_seq + 2.0 * keys) * d + (double)n_seq * H * ((out_src ? ld : 0) +
+                                                                                              (out_cls ? n_classes : 0))));
+  }
   return TVR_OK;
 }
 
@@ -3576,6 +3753,56 @@ int tvr_attention_pattern(tvr_model* m, const float* qkv, int32_t rows, const in
     rc = launch_pattern(m, fn, qkv, 0, 1, (const PatternSeq*)dbuf, n_seq, max_q + 1,
                         cls_bytes ? (const int32_t*)(dbuf + seq_bytes) : nullptr, n_classes, out_pattern, ld, out_mass,
                         cos_t, sin_t, st);
+  e = hipStreamSynchronize(st);
+  if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  (void)hipFree(dbuf);
+  return rc;
+}
+
+int tvr_attention_source(tvr_model* m, const float* qkv, int32_t rows, const int32_t* row0, const int32_t* qpos,
+                         int32_t n_seq, const float* g, const int32_t* cls, int32_t n_classes, float* out_src,
+                         int32_t ld, float* out_cls, const float* cos_t, const float* sin_t, void* stream) {
+  // every check on the host, before any device call
+  const char* fn = "tvr_attention_source";
+  auto bad = [&](const std::string& what) { return fail(TVR_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (!m) return bad("null model");
+  if (!qkv) return bad("null qkv");
+  if (!row0 || !qpos) return bad("null row0 / qpos");
+  if (!g) return bad("null g");
+  if (n_seq <= 0) return bad("n_seq must be positive");
+  if (rows <= 0) return bad("rows must be positive");
+  TVR_TRY(check_source_args(fn, cls, rows, n_classes, out_src, out_cls));
+  if ((cos_t == nullptr) != (sin_t == nullptr)) return bad("cos_t and sin_t must both be given or both be null");
+  if (((uintptr_t)qkv | (uintptr_t)g | (uintptr_t)cos_t | (uintptr_t)sin_t) & 15)
+    return bad("qkv, g and the rotary tables must be 16-byte aligned");
+  std::vector<PatternSeq> seqs(n_seq);
+  int max_q = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    const std::string at = " (sequence " + std::to_string(s) + ")";
+    if (qpos[s] < 0 || qpos[s] >= m->cfg.n_ctx) return bad("qpos outside [0, n_ctx)" + at);
+    if (row0[s] < 0 || (int64_t)row0[s] + qpos[s] >= rows) return bad("rows [row0, row0 + qpos] outside the qkv buffer" + at);
+    seqs[s] = PatternSeq{row0[s], qpos[s]};
+    max_q = std::max(max_q, qpos[s]);
+  }
+  if (out_src && ld <= max_q) return bad("ld must exceed the largest query position (" + std::to_string(max_q) + ")");
+  TVR_TRY(check_source(m->cfg, fn, n_seq, 1, max_q + 1));
+  const hipStream_t st = (hipStream_t)stream;
+  // descriptors, then the classes, in one temporary buffer
+  const size_t seq_bytes = align_up((size_t)n_seq * sizeof(PatternSeq));
+  const size_t cls_bytes = out_cls ? (size_t)rows * sizeof(int32_t) : 0;
+  char* dbuf = nullptr;
+  if (hipMalloc(&dbuf, seq_bytes + cls_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TVR_ERR_NOMEM, std::string(fn) + ": descriptor buffer");
+  }
+  hipError_t e = hipMemcpyAsync(dbuf, seqs.data(), (size_t)n_seq * sizeof(PatternSeq), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && cls_bytes) e = hipMemcpyAsync(dbuf + seq_bytes, cls, cls_bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // pageable host memory
+  int rc = e == hipSuccess ? TVR_OK : fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  if (rc == TVR_OK)
+    rc = launch_source(m, fn, qkv, 0, 1, (const PatternSeq*)dbuf, n_seq, max_q + 1, g, 0,
+                       cls_bytes ? (const int32_t*)(dbuf + seq_bytes) : nullptr, n_classes, out_src, ld, out_cls, 0, 1,
+                       cos_t, sin_t, st);
   e = hipStreamSynchronize(st);
   if (rc == TVR_OK && e != hipSuccess) rc = fail(TVR_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
   (void)hipFree(dbuf);

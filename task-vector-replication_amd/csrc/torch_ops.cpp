@@ -17,6 +17,9 @@
 //   tvr::logit_attribution tvr_trace_logit_attribution   (stack_head_results / accumulated_resid + logit_attrs)
 //   tvr::logit_lens      tvr_trace_logit_lens            (ln_final + unembed of every layer's resid_pre row)
 //   tvr::decode_rows     tvr_decode_rows                 (ln_final + unembed of any vectors)
+//   tvr::head_directions tvr_head_directions             (dirs @ W_O[l]: a direction in the heads' z coordinates)
+//   tvr::attention_source tvr_attention_source           (the source kernel alone, a test primitive)
+//   tvr::source_attribution tvr_trace_source_attribution (pattern[q, j] * (v[j] @ W_O[h]) . dir per key j)
 //
 // Every op enqueues on torch's CURRENT stream of the output device and
 // allocates its outputs through torch's caching allocator; host arrays
@@ -395,6 +398,97 @@ void logit_attribution(int64_t trace, const std::optional<at::Tensor>& pos, cons
         "tvr_trace_logit_attribution");
 }
 
+// out_g [n, d_model] = dirs [n, d_model] pulled back through W_O of one layer (tvr_head_directions).  dirs and
+// out_g: contiguous fp32 device tensors whose storage is 16-byte aligned (the engine refuses others).
+void head_directions(int64_t model, int64_t layer, const at::Tensor& dirs, int64_t d_model, at::Tensor& out_g) {
+  const c10::Device dev = out_g.device();
+  need_gpu(dev);
+  TORCH_CHECK_VALUE(dirs.dim() == 2 && dirs.size(0) > 0 && dirs.size(1) == d_model && dev_tensor(dirs, dev, at::kFloat),
+                    "tvr: dirs must be a contiguous fp32 tensor [n, d_model] on the output's device");
+  TORCH_CHECK_VALUE(dev_tensor(out_g, dev, at::kFloat) && out_g.sizes() == dirs.sizes(),
+                    "tvr: out_g must be a contiguous fp32 tensor [n, d_model]");
+  DeviceGuard guard(dev);
+  check(tvr_head_directions(as_model(model), (int32_t)layer, dirs.data_ptr<float>(), (int32_t)dirs.size(0),
+                            out_g.data_ptr<float>(), cur_stream(dev)),
+        "tvr_head_directions");
+}
+
+// The source kernel on a caller's one-layer buffer (tvr_attention_source).  qkv [rows, 3 d_model] and g
+// [n_seq, d_model]: contiguous fp32 device tensors, 16-byte aligned; row0 / qpos: CPU int32 [n_seq]; cls: CPU
+// int32 [rows] or None; out_src [n_seq, n_heads, ld] and out_cls [n_seq, n_heads, n_classes]: contiguous fp32
+// device tensors (offset views are fine), at least one of them; cos_t / sin_t: device tables or None (the model's).
+void attention_source(int64_t model, const at::Tensor& qkv, const at::Tensor& row0, const at::Tensor& qpos,
+                      const at::Tensor& g, const std::optional<at::Tensor>& cls, int64_t n_classes, int64_t d_model,
+                      int64_t n_heads, const std::optional<at::Tensor>& out_src, const std::optional<at::Tensor>& out_cls,
+                      const std::optional<at::Tensor>& cos_t, const std::optional<at::Tensor>& sin_t) {
+  TORCH_CHECK_VALUE(out_src.has_value() || out_cls.has_value(), "tvr: attention_source needs out_src or out_cls");
+  TORCH_CHECK_VALUE(!out_cls.has_value() || cls.has_value(), "tvr: out_cls needs cls");
+  TORCH_CHECK_VALUE(!cls.has_value() || n_classes > 0, "tvr: n_classes must be positive");
+  const int64_t n_seq = row0.numel();
+  TORCH_CHECK_VALUE(n_seq > 0 && qpos.numel() == n_seq, "tvr: row0 and qpos must have one entry per sequence");
+  const c10::Device dev = out_src.has_value() ? out_src->device() : out_cls->device();
+  need_gpu(dev);
+  TORCH_CHECK_VALUE(qkv.dim() == 2 && qkv.size(0) > 0 && qkv.size(1) == 3 * d_model && dev_tensor(qkv, dev, at::kFloat),
+                    "tvr: qkv must be a contiguous fp32 tensor [rows, 3 d_model] on the outputs' device");
+  TORCH_CHECK_VALUE(g.dim() == 2 && g.size(0) == n_seq && g.size(1) == d_model && dev_tensor(g, dev, at::kFloat),
+                    "tvr: g must be a contiguous fp32 tensor [n_seq, d_model] on the outputs' device");
+  TORCH_CHECK_VALUE(!cls.has_value() || cls->numel() == qkv.size(0), "tvr: cls must have one entry per row of qkv");
+  auto shaped = [&](const at::Tensor& t, int64_t last) {
+    return dev_tensor(t, dev, at::kFloat) && t.dim() == 3 && t.size(0) == n_seq && t.size(1) == n_heads &&
+           (last < 0 || t.size(2) == last);
+  };
+  TORCH_CHECK_VALUE(!out_src.has_value() || shaped(*out_src, -1),
+                    "tvr: out_src must be a contiguous fp32 tensor [n_seq, n_heads, ld]");
+  TORCH_CHECK_VALUE(!out_cls.has_value() || shaped(*out_cls, n_classes),
+                    "tvr: out_cls must be a contiguous fp32 tensor [n_seq, n_heads, n_classes]");
+  DeviceGuard guard(dev);
+  check(tvr_attention_source(as_model(model), qkv.data_ptr<float>(), (int32_t)qkv.size(0), host_i32(row0, "row0"),
+                             host_i32(qpos, "qpos"), (int32_t)n_seq, g.data_ptr<float>(), opt_host_i32(cls, "cls"),
+                             (int32_t)n_classes, out_src.has_value() ? out_src->data_ptr<float>() : nullptr,
+                             out_src.has_value() ? (int32_t)out_src->size(2) : 0,
+                             out_cls.has_value() ? out_cls->data_ptr<float>() : nullptr, in_f32(cos_t, dev, "cos_t"),
+                             in_f32(sin_t, dev, "sin_t"), cur_stream(dev)),
+        "tvr_attention_source");
+}
+
+// Per-source-token logit attribution of a trace (tvr_trace_source_attribution).  pos / contrast: CPU int32 [n_seq]
+// or None; target: CPU int32 [n_seq]; cls: CPU int32 [traced tokens] or None; out_src [n_seq, L, H, ld] and
+// out_cls [n_seq, L, H, n_classes]: contiguous fp32 device tensors (offset views are fine), at least one of them.
+void source_attribution(int64_t trace, const std::optional<at::Tensor>& pos, const at::Tensor& target,
+                        const std::optional<at::Tensor>& contrast, const std::optional<at::Tensor>& cls,
+                        int64_t n_classes, int64_t n_seq, int64_t n_layers, int64_t n_heads,
+                        const std::optional<at::Tensor>& out_src, const std::optional<at::Tensor>& out_cls) {
+  TORCH_CHECK_VALUE(trace != 0, "tvr: source_attribution needs a trace");
+  TORCH_CHECK_VALUE(out_src.has_value() || out_cls.has_value(), "tvr: source_attribution needs out_src or out_cls");
+  TORCH_CHECK_VALUE(!pos.has_value() || pos->numel() == n_seq, "tvr: pos must have one entry per traced sequence");
+  TORCH_CHECK_VALUE(target.numel() == n_seq, "tvr: target must have one entry per traced sequence");
+  TORCH_CHECK_VALUE(!contrast.has_value() || contrast->numel() == n_seq,
+                    "tvr: contrast must have one entry per traced sequence");
+  TORCH_CHECK_VALUE(!out_cls.has_value() || cls.has_value(), "tvr: out_cls needs cls");
+  TORCH_CHECK_VALUE(!cls.has_value() || n_classes > 0, "tvr: n_classes must be positive");
+  const c10::Device dev = out_src.has_value() ? out_src->device() : out_cls->device();
+  need_gpu(dev);
+  auto shaped = [&](const at::Tensor& t, int64_t last) {
+    return dev_tensor(t, dev, at::kFloat) && t.dim() == 4 && t.size(0) == n_seq && t.size(1) == n_layers &&
+           t.size(2) == n_heads && (last < 0 || t.size(3) == last);
+  };
+  TORCH_CHECK_VALUE(!out_src.has_value() || shaped(*out_src, -1),
+                    "tvr: out_src must be a contiguous fp32 tensor [n_seq, n_layers, n_heads, ld]");
+  TORCH_CHECK_VALUE(!out_cls.has_value() || shaped(*out_cls, n_classes),
+                    "tvr: out_cls must be a contiguous fp32 tensor [n_seq, n_layers, n_heads, n_classes]");
+  auto* tr = reinterpret_cast<tvr_trace*>(static_cast<intptr_t>(trace));
+  // the C ABI trusts cls to hold one entry per traced token: check it against the tensor here
+  TORCH_CHECK_VALUE(!cls.has_value() || cls->numel() == tvr_trace_num_tokens(tr),
+                    "tvr: cls must have one entry per traced token");
+  DeviceGuard guard(dev);
+  check(tvr_trace_source_attribution(tr, opt_host_i32(pos, "pos"), host_i32(target, "target"),
+                                     opt_host_i32(contrast, "contrast"), opt_host_i32(cls, "cls"), (int32_t)n_classes,
+                                     out_src.has_value() ? out_src->data_ptr<float>() : nullptr,
+                                     out_src.has_value() ? (int32_t)out_src->size(3) : 0,
+                                     out_cls.has_value() ? out_cls->data_ptr<float>() : nullptr, cur_stream(dev)),
+        "tvr_trace_source_attribution");
+}
+
 // The output pair of logit_lens / decode_rows: out_prob fp32 with `rows` elements, out_topk int32 [.., topk].
 c10::Device decode_outputs(const std::optional<at::Tensor>& targets, int64_t n_targets, int64_t rows, int64_t topk,
                            const std::optional<at::Tensor>& out_prob, const std::optional<at::Tensor>& out_topk) {
@@ -469,6 +563,11 @@ TORCH_LIBRARY(tvr, m) {
         "Tensor(a!)? out_prob, Tensor(b!)? out_topk) -> ()");
   m.def("decode_rows(int model, Tensor rows, Tensor? targets, int topk, int d_model, Tensor(a!)? out_prob, "
         "Tensor(b!)? out_topk) -> ()");
+  m.def("head_directions(int model, int layer, Tensor dirs, int d_model, Tensor(a!) out_g) -> ()");
+  m.def("attention_source(int model, Tensor qkv, Tensor row0, Tensor qpos, Tensor g, Tensor? cls, int n_classes, "
+        "int d_model, int n_heads, Tensor(a!)? out_src, Tensor(b!)? out_cls, Tensor? cos_t, Tensor? sin_t) -> ()");
+  m.def("source_attribution(int trace, Tensor? pos, Tensor target, Tensor? contrast, Tensor? cls, int n_classes, "
+        "int n_seq, int n_layers, int n_heads, Tensor(a!)? out_src, Tensor(b!)? out_cls) -> ()");
 }
 
 // Mixed host / device tensor arguments: one implementation for every backend key.
@@ -486,4 +585,7 @@ TORCH_LIBRARY_IMPL(tvr, CompositeExplicitAutograd, m) {
   m.impl("logit_attribution", &logit_attribution);
   m.impl("logit_lens", &logit_lens);
   m.impl("decode_rows", &decode_rows);
+  m.impl("head_directions", &head_directions);
+  m.impl("attention_source", &attention_source);
+  m.impl("source_attribution", &source_attribution);
 }

@@ -47,6 +47,12 @@ a window of layers and re-measure the answer, one sweep for prompts x windows:
 
   attention_knockout_effect, attention_knockout_by_role
 
+and the product of the two cheap signals, each head's direct logit attribution
+split over the roles of the keys it attends to (from which tokens a head
+carries the answer's logit; one pass over the trace's Q / K / V rows):
+
+  head_source_attribution, top_source_heads
+
 Drop-in notes
 * ``model`` is an ``amd.Model`` instead of a HookedTransformer; it must be
   passed (the reference's defaults bind a module-global model).
@@ -975,6 +981,53 @@ def knockout_role_prompts(model, contexts: Pairs, function_token: str, seperator
         answers.append(int(model.tokenizer.encode(pool[len_contexts][1])[0]))
     random.setstate(end)
     return prompts, roles, answers
+
+
+@range_checked
+def head_source_attribution(contexts: Pairs, function_token: str, seperator_token: Optional[str] = None,
+                            model: Model = None, num_contexts: int = 256, len_contexts: int = 4,
+                            contrast_answers=None) -> torch.Tensor:
+    """FROM WHICH tokens every head carries the answer's logit: the mean over
+    ``num_contexts`` prompts (``knockout_role_prompts``: the prompt stream of
+    ``head_attention_profile``, the answer the first token of the query pair's
+    label) of each head's direct logit attribution at the last position, split
+    over the roles of ``prompts.ROLES`` of the keys it attends to.
+    [n_layers, n_heads, len(ROLES)] on the device; its sum over the roles is
+    ``head_logit_attribution(prompts, answers).heads`` on the same prompts.  A
+    head can spread its attention over the demonstrations' labels and take all
+    of its push from one of them, or attend to BOS with a value that writes
+    nothing along the answer: ``head_attention_profile`` says where a head
+    looks, this what it brings back from there.  ``contrast_answers`` (one per
+    prompt, in ``head_logit_attribution``'s forms) attributes the logit difference.  One clean
+    forward into a trace and one pass over its Q / K / V rows
+    (``Trace.source_attribution``) per ``EXTRACT_BATCH`` prompts, no patched
+    forward."""
+    if num_contexts <= 0:
+        raise ValueError("num_contexts must be positive")
+    if len_contexts < 0 or len_contexts >= len(contexts):
+        raise ValueError("len_contexts must be smaller than the number of contexts (demos + one query)")
+    if contrast_answers is not None and len(contrast_answers) != num_contexts:
+        raise ValueError("Contrast answers must be of the same length as the prompts (num_contexts)")
+    prompts, roles, answers = knockout_role_prompts(model, contexts, function_token, seperator_token, num_contexts,
+                                                    len_contexts)
+    contrast = normalize_cie_inputs(model, [], contrast_answers)[1] if contrast_answers is not None else None
+    total = None
+    for a, b in _chunks(len(prompts), EXTRACT_BATCH):
+        seqs = prompts[a:b]
+        trace = model._sweep_trace(len(seqs), sum(len(s) for s in seqs))
+        model.forward_clean(seqs, trace=trace)
+        part = trace.source_attribution(answers[a:b], contrast=contrast[a:b] if contrast is not None else None,
+                                        classes=roles[a:b], n_classes=len(ROLES))[1].sum(0)  # prompts in order
+        total = part if total is None else total + part
+    return total / num_contexts
+
+
+def top_source_heads(profile: torch.Tensor, role, num_heads: int) -> List[Tuple[int, int]]:
+    """The ``num_heads`` (layer, head) pairs of a ``head_source_attribution``
+    that carry the most attribution from ``role`` (a name of ``prompts.ROLES``
+    or its index), highest first (torch.topk's order and tie rule, as
+    ``top_attention_heads``)."""
+    return top_attention_heads(profile, role, num_heads)
 
 
 @range_checked

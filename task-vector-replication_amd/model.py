@@ -12,6 +12,9 @@ token helpers, and drives the engine's batched entry points:
   layer at once (replaces ``run_with_cache`` + a Python mean over prompts);
 * ``logit_attribution`` / ``head_attribution`` — every head's and every layer's
   push on a token's logit from a trace (``stack_head_results`` + ``logit_attrs``);
+* ``source_attribution`` / ``head_directions`` — every head's push split over the
+  key tokens it attends to (pattern × value-weighted attribution, per key or per
+  class of keys);
 * ``logit_lens`` / ``decode_rows`` — residual rows of every layer, or any
   vectors, through the final LayerNorm and the unembedding.
 
@@ -171,6 +174,14 @@ class Trace:
         """Direct logit attribution at ``pos[s]`` of every traced sequence:
         ``(heads [n_seq, L, H], resid [n_seq, L + 1])``; see ``Model.logit_attribution``."""
         return self.model.logit_attribution(self, targets, contrast=contrast, positions=pos)
+
+    def source_attribution(self, targets, contrast=None, pos: Optional[Sequence[int]] = None, classes=None,
+                           n_classes: int = 0, want_keys: bool = False):
+        """Every head's direct logit attribution at ``pos[s]`` split over the keys
+        it attends to: ``(src [n_seq, L, H, max(pos) + 1] or None,
+        by_class [n_seq, L, H, n_classes] or None)``; see ``Model.source_attribution``."""
+        return self.model.source_attribution(self, targets, contrast=contrast, positions=pos, classes=classes,
+                                             n_classes=n_classes, want_keys=want_keys)
 
     def logit_lens(self, targets=None, pos: Optional[Sequence[int]] = None, topk: int = 0):
         """Every layer's residual row at ``pos[s]`` decoded through the final
@@ -790,6 +801,80 @@ class Model(TokenizerMixin):
         self._check_range("tvr_trace_logit_attribution")  # (a deferred clean forward may have run)
         trace._pending_out = None
         return heads, resid
+
+    def head_directions(self, layer: int, dirs: torch.Tensor) -> torch.Tensor:
+        """Directions pulled back through ``W_O`` of ``layer`` into the heads'
+        ``z`` coordinates (tvr_head_directions): ``g[i] = dirs[i] @ W_O[layer]ᵀ``
+        in ``hook_z``'s flattened (head, d_head) order, so that
+        ``(z[h] @ W_O[layer, h]) · dirs[i] = z[h] · g[i, h·dh:(h+1)·dh]`` for any
+        ``z``.  ``dirs`` ``[n, d_model]`` fp32 on the model device; ``[n, d_model]``.
+        The bits of a row depend on that row alone."""
+        cfg = self.cfg
+        if not 0 <= int(layer) < cfg.n_layers:
+            raise ValueError("layer out of range")
+        if not isinstance(dirs, torch.Tensor) or dirs.dim() != 2 or dirs.shape[1] != cfg.d_model or dirs.shape[0] == 0:
+            raise ValueError("dirs must be a tensor [n, d_model]")
+        if dirs.device != self.device or dirs.dtype != torch.float32:
+            raise ValueError("dirs must be fp32 on the model device")
+        dirs = dirs.contiguous()
+        if dirs.data_ptr() % 16:
+            dirs = dirs.clone()
+        out = torch.empty(dirs.shape[0], cfg.d_model, device=self.device)
+        self._op("head_directions", self._h.value, int(layer), dirs, cfg.d_model, out)
+        return out
+
+    @staticmethod
+    def _key_classes(classes, n_classes: int, lens: np.ndarray) -> np.ndarray:
+        """``capture_pattern``'s class checks: int32 [traced tokens] from a flat
+        list or one list per sequence, every id in ``[-1, n_classes)``."""
+        n = int(lens.shape[0])
+        if not 0 < n_classes <= _lib.PATTERN_MAX_CLASSES:
+            raise ValueError(f"n_classes must be in [1, {_lib.PATTERN_MAX_CLASSES}]")
+        if len(classes) == n and all(not np.isscalar(c) for c in classes):  # one list per sequence
+            if any(len(c) != t for c, t in zip(classes, lens)):
+                raise ValueError("classes must have one entry per traced token")
+            classes = [x for c in classes for x in c]
+        cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+        if cls.shape[0] != int(lens.sum()):
+            raise ValueError("classes must have one entry per traced token")
+        if np.any(cls < -1) or np.any(cls >= n_classes):
+            raise ValueError("a class lies outside [-1, n_classes)")
+        return cls
+
+    def source_attribution(self, trace: Trace, targets, contrast=None, positions: Optional[Sequence[int]] = None,
+                           classes=None, n_classes: int = 0, want_keys: bool = False):
+        """From which key tokens every head carries the answer's logit
+        (tvr_trace_source_attribution): ``(src, by_class)`` with ``src``
+        ``[n, L, H, max(positions) + 1]`` (``want_keys``, else ``None``),
+        ``src[s, l, h, j] = pattern[l][h, q, j] · ((hook_v[l][j, h] @ W_O[l, h]) · u / σ)``
+        for the keys ``j ≤ q`` and zero beyond, and ``by_class``
+        ``[n, L, H, n_classes]`` (``classes`` given, else ``None``) its sums over
+        the keys of each class.  ``u``, σ, ``targets``, ``contrast`` and
+        ``positions`` as in ``logit_attribution``, whose ``heads`` are the sums of
+        ``src`` over the keys (``b_V`` is zero in the processed model);
+        ``classes`` as in ``Trace.attention_mass``.  Every argument is checked
+        before the engine is called.  Bitwise reproducible for a given trace."""
+        n, pos = self._trace_queries(trace, positions)
+        tg = self._token_ids(targets, n, "targets")
+        ct = self._token_ids(contrast, n, "contrast") if contrast is not None else None
+        if not want_keys and classes is None:
+            raise ValueError("nothing to attribute: ask for the keys or give classes")
+        lens = np.asarray(trace.seq_lens, dtype=np.int64)
+        cls = None
+        if classes is not None:
+            n_classes = int(n_classes)
+            cls = Model._key_classes(classes, n_classes, lens)
+        cfg = self.cfg
+        ld = int(pos.max() if pos is not None else lens.max() - 1) + 1
+        src = torch.empty(n, cfg.n_layers, cfg.n_heads, ld, device=self.device) if want_keys else None
+        by_class = torch.empty(n, cfg.n_layers, cfg.n_heads, n_classes, device=self.device) if cls is not None else None
+        self._op("source_attribution", trace._h.value, torch.from_numpy(pos) if pos is not None else None,
+                 torch.from_numpy(tg), torch.from_numpy(ct) if ct is not None else None,
+                 torch.from_numpy(cls) if cls is not None else None, n_classes if cls is not None else 0, n,
+                 cfg.n_layers, cfg.n_heads, src, by_class)
+        self._check_range("tvr_trace_source_attribution")  # (a deferred clean forward may have run)
+        trace._pending_out = None
+        return src, by_class
 
     def logit_lens(self, trace: Trace, targets=None, positions: Optional[Sequence[int]] = None, topk: int = 0):
         """Every layer's residual row at the query position through the final
